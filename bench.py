@@ -26,6 +26,15 @@ it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
                     [--config volcano|cstr|dmtm_drc|ch4|synthetic]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, the status counts of the last step).
+--dump-outputs DIR also writes the arrays of the last timed step as
+DIR/<name>.npy.  --full adds what takes runs or work of its own: kernel (1)
+timed alone, the fp64 roofline of the solver launches (`roofline`) and the
+oracle timed on the host cores (`cpu_baseline`; --no-cpu-baseline leaves it
+out); without --full both keys are null.
 """
 import argparse
 import ctypes as C
@@ -287,7 +296,8 @@ def launch_ranks(n, argv):
 # ----------------------------------------------------------------------------
 class Workload:
     """One config's per-rank share: device inputs, a step() that launches the
-    solve, and the result tensors of the last step."""
+    solve, and the result tensors of the last step (outputs(): every array
+    the step's caller receives, by name, conditions along the last axis)."""
     kernel_name = ''
     units = 'solves'
     tag = ''
@@ -358,6 +368,8 @@ def _solve_workload(wl, sim, net, plan, n, T, p, desc, tof_terms, steady, activi
     wl.status = lambda: wl.out['status'][:n]
     wl.nsteps = lambda: wl.out['nsteps'][:n]
     wl.result = lambda: wl.out['tof'][:n]
+    wl.outputs = lambda: dict(y=wl.out['y'][:, :n], tof=wl.out['tof'][:n], status=wl.out['status'][:n],
+                              nsteps=wl.out['nsteps'][:n])
     # algorithmic HBM bytes of one solve launch: kf, kr in; y, tof, status, steps out
     wl.algo_bytes = n * (16 * net.NRXN + 8 * net.NDYN + 8 + 4 + 4)
     return wl
@@ -521,6 +533,7 @@ def dmtm_drc_workload(args, rank, world):
                                 _ptr(ns), sp))
     wl.step, wl.rate_constants = step, None
     wl.status, wl.nsteps, wl.result = (lambda: st[:n]), (lambda: ns[:n]), (lambda: tof0[:n])
+    wl.outputs = lambda: dict(xi=xi[:, :n], tof0=tof0[:n], status=st[:n], nsteps=ns[:n])
     wl.net, wl.plan, wl.n_local = net, plan, n
     wl.algo_bytes = n * (8 * net.NRXN + 8 + 4 + 4)
     wl.kernel_name = 'k_solve_grp<16, 16>'
@@ -559,10 +572,42 @@ def cpu_standin_workload(args, rank, world):
     wl.step = lambda sp: None
     wl.rate_constants = None
     wl.status, wl.nsteps, wl.result = (lambda: st), (lambda: torch.ones(E1.size, dtype=torch.int32)), (lambda: val)
+    wl.outputs = lambda: dict(result=wl.result(), status=wl.status(), nsteps=wl.nsteps())
     wl.config = {'workload': 'CPU stand-in of the volcano grid layout', 'global_grid': list(wl.global_grid),
                  'grid_per_gpu': [rows, G], 'parallelism': 'dp%d' % world}
     wl.data = 'stand-in'
     return wl
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6     # --dump-outputs: all files of all ranks together stay below 64 MB
+
+
+def dump_outputs(outputs, outdir, rank=0, world=1, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write the arrays of `outputs` (name -> tensor, conditions along the last
+    axis) as outdir/<name>.npy (outdir/<name>.rank<r>.npy at world > 1):
+    float32 / float64 as they are, integers as float64 (exact).  Where the whole
+    would exceed this rank's share of `budget`, the same seeded, sorted sample
+    of conditions is kept of every array and its indices are written as
+    sample_index.  Returns {file name: shape}."""
+    arrs = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    n = next(iter(arrs.values())).shape[-1] if arrs else 0
+    per_cond = sum(a.dtype.itemsize * (a.size // max(n, 1)) for a in arrs.values())
+    share = budget // max(world, 1)
+    if n * per_cond > share:
+        keep = share // (per_cond + 8)               # + 8: the sample's index itself
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=int(keep), replace=False))
+        arrs = {name: a[..., idx] for name, a in arrs.items()}
+        arrs['sample_index'] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, a in arrs.items():
+        fn = '%s.npy' % name if world == 1 else '%s.rank%d.npy' % (name, rank)
+        np.save(os.path.join(outdir, fn), np.ascontiguousarray(a))
+        written[fn] = list(a.shape)
+    return written
 
 
 def build_parser():
@@ -578,7 +623,13 @@ def build_parser():
     ap.add_argument('--grid', type=int, default=1024)
     ap.add_argument('--n', type=int, default=0, help='conditions of the non-volcano configs (0: config default)')
     ap.add_argument('--max-steps', type=int, default=200000, help='integrator step budget per condition (library default)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the arrays of the last timed step as DIR/<name>.npy (float32 / float64, at most '
+                         '64 MB in all: a fixed seeded sample of the conditions beyond that)')
+    ap.add_argument('--full', action='store_true',
+                    help='also time kernel (1) alone, state the roofline of the solver launches and time the CPU '
+                         'baseline (off by default: a plain run measures the headline figure only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--cpu-points', type=int, default=4000,
                     help='CPU baseline sample (stopped after 25 s of wall time)')
     ap.add_argument('--no-newton', action='store_true', help='A/B diagnostic: transient only (not the bench workload)')
@@ -628,6 +679,8 @@ def main(argv=None):
         args.steps = 20 if args.config == 'volcano' else 5
     if args.warmup is None:
         args.warmup = 10 if args.config == 'volcano' else 2
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be at least 1 and --warmup at least 0')
     _heartbeat()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -683,7 +736,7 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     solve_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else 0.0
     k1_ms = 0.0
-    if wl.rate_constants is not None and ev:
+    if args.full and wl.rate_constants is not None and ev:
         # kernel (1) alone, same stream, to split pck_solve's two launches
         e1 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
         for a, b in e1:
@@ -699,11 +752,15 @@ def main(argv=None):
     counts = torch.tensor([int((st == 0).sum()), int((st == 4).sum()), int(((st != 0) & (st != 4) & (st != 5)).sum()),
                            n, int((st == 1).sum()), int((st == 2).sum()), int((st == 3).sum()), int((st == 5).sum())],
                           dtype=torch.int64, device=dev)
-    ns = wl.nsteps().double()
-    steps_local = float(ns.sum())
-    pad = (-n) % 64
-    wave_max = torch.nn.functional.pad(ns, (0, pad)).reshape(-1, 64).max(dim=1).values if n else ns
-    lane_eff = float(ns.mean() / wave_max.mean()) if n else 1.0
+    if args.dump_outputs:
+        written = dump_outputs(wl.outputs(), args.dump_outputs, rank, world)
+        log('rank %d: outputs of the last step in %s: %s' % (rank, args.dump_outputs, json.dumps(written)))
+    if args.full:
+        ns = wl.nsteps().double()
+        steps_local = float(ns.sum())
+        pad = (-n) % 64
+        wave_max = torch.nn.functional.pad(ns, (0, pad)).reshape(-1, 64).max(dim=1).values if n else ns
+        lane_eff = float(ns.mean() / wave_max.mean()) if n else 1.0
     if dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -727,7 +784,7 @@ def main(argv=None):
 
     if rank == 0:
         roof, cpu_line = None, None
-        if not cpu:
+        if args.full and not cpu:
             fps = flops_per_step(wl.plan)
             fl_struct = fps * steps_local
             # a group network of at most 16 species ran on the quad kernel
