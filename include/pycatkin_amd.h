@@ -29,6 +29,8 @@
  *                          SteadyStateSolver.solve_ode        pycatkin/classes/solver.py:374
  *                          System.run_and_return_tof / activity old_system.py:470,517
  *   pck_drc             <- System.degree_of_rate_control      old_system.py:490
+ *   pck_energy_span     <- Energy.construct_energy_landscape  pycatkin/classes/energy.py:39
+ *                          Energy.evaluate_energy_span_model  energy.py:238
  *
  * All functions return 0 on success and a negative PCK_E_* code on failure;
  * pck_last_error() returns a message for the calling thread.  Device pointers
@@ -47,7 +49,7 @@
 extern "C" {
 #endif
 
-#define PCK_ABI_VERSION 6
+#define PCK_ABI_VERSION 7
 
 /* error codes */
 #define PCK_OK 0
@@ -66,6 +68,7 @@ extern "C" {
 #define PCK_MAX_EXP 255     /* stoichiometric exponent */
 #define PCK_MAX_CONS 4      /* conservation laws */
 #define PCK_MAX_TOF 16      /* TOF terms */
+#define PCK_MAX_PES 64      /* entries of an energy landscape (pck_energy_span) */
 
 /* int32 blob header slots (ip[0..PCK_I_HDR)) */
 enum {
@@ -291,6 +294,46 @@ int pck_solve(const pck_network* net, const pck_conditions* cond,
 int pck_drc(const pck_network* net, const pck_conditions* cond,
             const pck_solve_params* prm, double* xi, int64_t ld_xi,
             double* tof0, int32_t* status, int32_t* nsteps, void* stream);
+
+/* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
+ * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program
+ * register that holds its energy (eV).  Entry 0 is the reference every energy
+ * is taken relative to, and entry n_pts-1 the end of the cycle (its energy is
+ * the reaction energy); neither may be a transition state.  Passed from host
+ * memory. */
+typedef struct {
+    int32_t n_pts;               /* N */
+    int32_t reg[PCK_MAX_PES];    /* register (< NREG) of entry k */
+    uint64_t ts_mask;            /* bit k set: entry k is a transition state */
+} pck_landscape;
+
+/* Outputs of pck_energy_span (device pointers; any may be NULL).  nTi = TS
+ * entries, nIj-1 = intermediates among entries 1..N-2 (energy.py:250-255). */
+typedef struct {
+    double* tof;                 /* [n] turnover frequency (1/s); may underflow to 0 */
+    double* espan;               /* [n] E(TDTS) - E(TDI) (eV) */
+    double* eapp;                /* [n] apparent activation energy (kJ/mol, energy.py:300), from ln tof */
+    double* dgrxn;               /* [n] energy of the last entry (eV) */
+    int32_t* i_tdts;             /* [n] landscape index of the TOF-determining TS (-1: non-finite energy) */
+    int32_t* i_tdi;              /* [n] ... of the TOF-determining intermediate */
+    double* x_ts;                /* [nTi][ld_x] TS contributions (num_i), TS entries in landscape order */
+    double* x_int;               /* [nIj-1][ld_x] intermediate contributions (num_j), likewise */
+    int64_t ld_x;
+    double* energy; int64_t ld_e;   /* [N][ld_e] landscape energies (eV) relative to entry 0 */
+} pck_span_outputs;
+
+/* Energy-span model of a landscape for every condition, one launch:
+ * the energy program -> the N landscape energies -> TOF, energy span, the
+ * TOF-determining states and every state's contribution
+ * (Energy.construct_energy_landscape energy.py:39 +
+ *  Energy.evaluate_energy_span_model energy.py:238).  The sums of exponentials
+ * are carried as a shift plus a sum and the TOF in logs, so no energy makes
+ * an output overflow; a condition with a non-finite energy gets NaN outputs
+ * and indices -1.  Takes an energy-only network (NDYN = NRXN = 0) or any other.
+ * PCK_E_ARG: N outside 4..PCK_MAX_PES, a register out of range, entry 0 or
+ * N-1 a TS, no TS or no intermediate among entries 1..N-2. */
+int pck_energy_span(const pck_network* net, const pck_conditions* cond, const pck_landscape* pes,
+                    const pck_span_outputs* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@ All compute runs in the HIP kernels of libpycatkin_amd.so (gfx950); the
 Python layer compiles networks and marshals device buffers."""
 from .energy import TSYM, Descriptor, LinearForm, clamp0  # noqa: F401
 from .classes.state import ScalingState, State  # noqa: F401
+from .classes.energy import Energy  # noqa: F401
 from .classes.reaction import Reaction, ReactionDerivedReaction, UserDefinedReaction  # noqa: F401
 from .classes.reactor import CSTReactor, InfiniteDilutionReactor, Reactor  # noqa: F401
 from .classes.system import SteadyStateResults, System  # noqa: F401

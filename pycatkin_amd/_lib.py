@@ -16,9 +16,9 @@ LIB_PATH = os.environ.get('PCK_LIB') or os.path.join(_HERE, 'libpycatkin_amd.so'
 # symbols declared in include/pycatkin_amd.h (checked by tests/test_capi.py)
 EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_network_destroy',
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
-            'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc')
+            'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span')
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # header slot indices (must match the enums of include/pycatkin_amd.h)
 I_VERSION, I_NDESC, I_NTH, I_NREG, I_NRXN, I_NDYN, I_NFIX, I_NCONS, I_NTOF = range(9)
@@ -31,6 +31,7 @@ IP_MIN = I_HDR + D_NBLK
 RX_ARRHENIUS, RX_ADS_KEQ, RX_DES_KEQ, RX_ADS_KDES, RX_DES_KDES = range(5)
 TH_VIB, TH_GAS = 1, 2
 MAX_DYN, MAX_DYN_LANE, MAX_RXN, MAX_CONS, MAX_TOF = 64, 8, 256, 4, 16
+MAX_PES = 64
 PLAN_AUTO, PLAN_RUNTIME, PLAN_GROUP = 0, 1, 2
 ST_OK, ST_MAXSTEPS, ST_STEPFAIL, ST_NONFINITE, ST_NEWTON, ST_NEWTON_LOOSE, ST_DRC_MIXED = range(7)
 E_ARG, E_HIP, E_SIZE = -1, -2, -3
@@ -60,6 +61,16 @@ class Outputs(C.Structure):
                 ('traj', C.c_void_p), ('ld_traj', C.c_int64)]
 
 
+class Landscape(C.Structure):
+    _fields_ = [('n_pts', C.c_int32), ('reg', C.c_int32 * MAX_PES), ('ts_mask', C.c_uint64)]
+
+
+class SpanOutputs(C.Structure):
+    _fields_ = [('tof', C.c_void_p), ('espan', C.c_void_p), ('eapp', C.c_void_p), ('dgrxn', C.c_void_p),
+                ('i_tdts', C.c_void_p), ('i_tdi', C.c_void_p), ('x_ts', C.c_void_p), ('x_int', C.c_void_p),
+                ('ld_x', C.c_int64), ('energy', C.c_void_p), ('ld_e', C.c_int64)]
+
+
 _lib = None
 
 
@@ -79,6 +90,9 @@ def load():
     vp, i64, i32p = C.c_void_p, C.c_int64, C.POINTER(C.c_int32)
     lib.pck_abi_version.restype = C.c_int
     lib.pck_last_error.restype = C.c_char_p
+    # before any symbol is bound: an older library lacks the newer ones
+    if lib.pck_abi_version() != ABI_VERSION:
+        raise RuntimeError('pycatkin_amd: ABI mismatch (library %d, python %d)' % (lib.pck_abi_version(), ABI_VERSION))
     lib.pck_network_create.argtypes = [vp, i64, vp, i64, C.POINTER(vp)]
     lib.pck_network_destroy.argtypes = [vp]
     lib.pck_network_dims.argtypes = [vp, i32p]
@@ -91,11 +105,10 @@ def load():
     lib.pck_reaction_rates.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp, i64, vp]
     lib.pck_solve.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(Outputs), vp]
     lib.pck_drc.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
+    lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
     for name in EXPORTED:
         if name not in ('pck_last_error',):
             getattr(lib, name).restype = C.c_int
-    if lib.pck_abi_version() != ABI_VERSION:
-        raise RuntimeError('pycatkin_amd: ABI mismatch (library %d, python %d)' % (lib.pck_abi_version(), ABI_VERSION))
     _lib = lib
     return lib
 

@@ -114,6 +114,144 @@ __global__ void __launch_bounds__(64) k_energies(NetView nv, CondView cv, double
     for (int r = 0; r < nv.NREG; ++r) out[r * ld_out + c] = f[(rb + r) * fs];
 }
 
+// ----------------------------------------------------------------------------
+// energy-span model (energy.py:39-60 landscape, :238-318 span), one lane per
+// condition.  The lane's column holds its nfeat features and one work value per
+// landscape entry (LDS when they fit, else the HBM scratch).
+//
+// With x_k = E_k / RT (E_k relative to entry 0), d = -x_{N-1}, TS entries i and
+// intermediates j among 1..N-2, the reference sums exp(x_i - x_j + d [i >= j])
+// over all pairs (:259-274).  Each term is a product A_i B_j D_ij with
+// A_i = exp(x_i - max_i x_i), B_j = exp(-x_j - max_j(-x_j)) and D one of
+// exp(d - dm), exp(-dm), dm = max(d, 0), so the row sums (num_i) and column sums
+// (num_j) come from prefix sums of B and A in an upward scan and suffix sums in
+// a downward one: 2 (N-2) + 2 exponentials instead of nTi (nIj-1) for each of
+// rows and columns.  No factor exceeds 1 and the sum is carried next to its shift
+// max_i + max_j + dm.  Where the three maxima do not meet in one pair the
+// shifted sum can lose its small terms to underflow: below 1e-200 (lost terms
+// then weigh < 1e-100 of it) the lane sums the pairs one by one, shifted
+// by their exact maximum.
+// ----------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck_landscape pes, pck_span_outputs o,
+                                                    double* feat, int64_t fs) {
+    extern __shared__ double lds_feat[];
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cv.n) return;
+    const double T = cv.T[c * cv.sT];
+    double* f = feat ? feat + c : lds_feat + threadIdx.x;
+    if (!feat) fs = blockDim.x;
+    thermo_features(nv, T, cv.p[c * cv.sp], cv.desc + c * cv.s_desc, cv.ld_desc, f, fs);
+    const int rb = 2 + nv.D + 3 * nv.NTH;
+    const int N = pes.n_pts;
+    // work value of entry k: the thermal feature columns are dead once the
+    // registers are formed, so it takes one of those, and a column past the
+    // features only when the landscape has more entries than there are
+    const int nth3 = 3 * nv.NTH;
+    auto W = [&](int k) -> double& { return f[(k < nth3 ? 2 + nv.D + k : nv.nfeat + (k - nth3)) * fs]; };
+    const double RT = Rgas * T;
+    const double beta = EV2JMOL / RT;                // eV -> J/mol -> units of RT (energy.py:257-269)
+    const double e0 = f[(rb + pes.reg[0]) * fs];
+    auto E = [&](int k) { return f[(rb + pes.reg[k]) * fs] - e0; };
+    auto is_ts = [&](int k) { return (pes.ts_mask >> k) & 1ull; };
+
+    bool ok = T > 0.0;
+    double ma = -INFINITY, mb = -INFINITY;
+    for (int k = 0; k < N; ++k) {
+        const double e = E(k);
+        if (o.energy) o.energy[k * o.ld_e + c] = e;
+        const double x = e * beta;
+        ok = ok && (x - x == 0.0);
+        if (k >= 1 && k <= N - 2) {
+            if (is_ts(k)) ma = fmax(ma, x); else mb = fmax(mb, -x);
+        }
+    }
+    if (!ok) {                                       // a non-finite energy (or T <= 0): NaN, no indices
+        const double q = NAN;
+        if (o.tof) o.tof[c] = q;
+        if (o.espan) o.espan[c] = q;
+        if (o.eapp) o.eapp[c] = q;
+        if (o.dgrxn) o.dgrxn[c] = q;
+        if (o.i_tdts) o.i_tdts[c] = -1;
+        if (o.i_tdi) o.i_tdi[c] = -1;
+        int ri = 0, rj = 0;
+        for (int k = 1; k <= N - 2; ++k) {
+            if (is_ts(k)) { if (o.x_ts) o.x_ts[ri * o.ld_x + c] = q; ++ri; }
+            else { if (o.x_int) o.x_int[rj * o.ld_x + c] = q; ++rj; }
+        }
+        return;
+    }
+    const double d = -E(N - 1) * beta;               // -drxn / RT
+    const double dm = fmax(d, 0.0);
+    const double ed1 = exp(d - dm), ed0 = exp(-dm);  // pairs i >= j carry exp(d), the others 1
+    // upward: pairs whose partner lies below k
+    double PB = 0.0, PA = 0.0;
+    for (int k = 1; k <= N - 2; ++k) {
+        const double x = E(k) * beta;
+        if (is_ts(k)) { const double g = exp(x - ma); W(k) = g * (ed1 * PB); PA += g; }
+        else { const double g = exp(-x - mb); W(k) = g * (ed0 * PA); PB += g; }
+    }
+    // downward: pairs whose partner lies above k; den = the sum of the TS rows
+    double SB = 0.0, SA = 0.0, den = 0.0;
+    for (int k = N - 2; k >= 1; --k) {
+        const double x = E(k) * beta;
+        if (is_ts(k)) {
+            const double g = exp(x - ma), r = W(k) + g * (ed0 * SB);
+            W(k) = r; den += r; SA += g;
+        } else {
+            const double g = exp(-x - mb);
+            W(k) = W(k) + g * (ed1 * SA); SB += g;
+        }
+    }
+    double shift = ma + mb + dm;
+    if (!(den > 1.0e-200)) {
+        double M = -INFINITY;
+        for (int i = 1; i <= N - 2; ++i) {
+            if (!is_ts(i)) continue;
+            const double xi = E(i) * beta;
+            for (int j = 1; j <= N - 2; ++j)
+                if (!is_ts(j)) M = fmax(M, xi - E(j) * beta + (i >= j ? d : 0.0));
+        }
+        den = 0.0;
+        for (int k = 1; k <= N - 2; ++k) {
+            const bool tk = is_ts(k);
+            const double xk = E(k) * beta;
+            double s = 0.0;
+            for (int l = 1; l <= N - 2; ++l) {
+                if ((bool)is_ts(l) == tk) continue;
+                const double xl = E(l) * beta;
+                const bool ge = tk ? k >= l : l >= k;                  // TS index >= intermediate index
+                s += exp((tk ? xk - xl : xl - xk) + (ge ? d : 0.0) - M);
+            }
+            W(k) = s;
+            if (tk) den += s;
+        }
+        shift = M;
+    }
+    // energy.py:292,300 in logs: ln tof = ln(kB T / h) - drxn/RT - 1 - ln den
+    const double lt = d - 1.0 - (shift + log(den));
+    if (o.tof) o.tof[c] = exp(log(kB * T / hP) + lt);
+    if (o.eapp) o.eapp[c] = lt * (-RT) * 1.0e-3;
+    if (o.dgrxn) o.dgrxn[c] = E(N - 1);
+    // energy.py:275-287: contributions; the first index attaining the maximum
+    int it = -1, ii = -1, ri = 0, rj = 0;
+    double bt = -1.0, bi = -1.0;
+    for (int k = 1; k <= N - 2; ++k) {
+        const double v = W(k) / den;
+        if (is_ts(k)) {
+            if (o.x_ts) o.x_ts[ri * o.ld_x + c] = v;
+            ++ri;
+            if (v > bt) { bt = v; it = k; }
+        } else {
+            if (o.x_int) o.x_int[rj * o.ld_x + c] = v;
+            ++rj;
+            if (v > bi) { bi = v; ii = k; }
+        }
+    }
+    if (o.i_tdts) o.i_tdts[c] = it;
+    if (o.i_tdi) o.i_tdi[c] = ii;
+    if (o.espan) o.espan[c] = (it > 0 && ii > 0) ? E(it) - E(ii) : (double)NAN;
+}
+
 #include "mk_solver.h"
 
 // The solver kernels are compiled in translation units of their own in the
@@ -610,6 +748,48 @@ extern "C" int pck_energies(const pck_network* net, const pck_conditions* cond, 
     }
     hipLaunchKernelGGL(k_energies, dim3((unsigned)((n + RC_BLOCK - 1) / RC_BLOCK)), dim3(RC_BLOCK), shm,
                        (hipStream_t)stream, net->nv, cview(cond), feat, fs, out, ld_out);
+    HIPCHK(hipGetLastError());
+    return PCK_OK;
+}
+
+extern "C" int pck_energy_span(const pck_network* net, const pck_conditions* cond, const pck_landscape* pes,
+                               const pck_span_outputs* out, void* stream) {
+    int rc = check_cond(net, cond, false);
+    if (rc) return rc;
+    if (!pes || !out) return fail(PCK_E_ARG, "null landscape/outputs%s", "");
+    const int N = pes->n_pts;
+    if (N < 4 || N > PCK_MAX_PES) return fail(PCK_E_ARG, "landscape has%s %lld entries (4..64)", "", N);
+    for (int k = 0; k < N; ++k)
+        if (pes->reg[k] < 0 || pes->reg[k] >= net->nv.NREG)
+            return fail(PCK_E_ARG, "landscape entry%s %lld names a register outside the energy program", "", k);
+    pck_landscape ls = *pes;
+    if (N < 64) ls.ts_mask &= (1ull << N) - 1ull;
+    if (ls.ts_mask & 1ull) return fail(PCK_E_ARG, "the first landscape entry is a transition state%s", "");
+    if ((ls.ts_mask >> (N - 1)) & 1ull) return fail(PCK_E_ARG, "the last landscape entry is a transition state%s", "");
+    const int nts = __builtin_popcountll(ls.ts_mask);          // all among entries 1..N-2 now
+    if (nts == 0) return fail(PCK_E_ARG, "landscape has no transition state%s", "");
+    if (nts == N - 2) return fail(PCK_E_ARG, "landscape has no intermediate between its first and last entry%s", "");
+    const int64_t n = cond->n;
+    if (n == 0) return PCK_OK;
+    if ((out->x_ts || out->x_int) && out->ld_x < n) return fail(PCK_E_ARG, "bad contribution output%s (ld_x %lld)", "", out->ld_x);
+    if (out->energy && out->ld_e < n) return fail(PCK_E_ARG, "bad landscape energy output%s (ld_e %lld)", "", out->ld_e);
+    // the lane's features and its N work values share one column; the work
+    // values reuse the 3 NTH thermal feature columns first (k_energy_span)
+    const int ncol = net->nv.nfeat + std::max(0, N - 3 * net->nv.NTH);
+    StreamScratch scr;
+    size_t shm = 0;
+    double* feat = nullptr;
+    int64_t fs = 0;
+    if (rc_feat_in_lds(ncol)) {
+        shm = sizeof(double) * (size_t)ncol * RC_BLOCK;
+    } else {
+        rc = salloc(scr, sizeof(double) * (size_t)ncol * n, (hipStream_t)stream);
+        if (rc) return rc;
+        feat = scr.as<double>();
+        fs = n;
+    }
+    hipLaunchKernelGGL(k_energy_span, dim3((unsigned)((n + RC_BLOCK - 1) / RC_BLOCK)), dim3(RC_BLOCK), shm,
+                       (hipStream_t)stream, net->nv, cview(cond), ls, *out, feat, fs);
     HIPCHK(hipGetLastError());
     return PCK_OK;
 }

@@ -147,6 +147,48 @@ class DeviceNetwork:
         L.check(self.lib.pck_energies(self.h, C.byref(c), _ptr(out), out.shape[1], _stream(torch)))
         return out[:self.NREG, :n]
 
+    SPAN_OUTPUTS = ('tof', 'espan', 'eapp', 'dgrxn', 'i_tdts', 'i_tdi', 'x_ts', 'x_int', 'energy')
+
+    def energy_span(self, n, T, p, landscape, desc=None, want=SPAN_OUTPUTS):
+        """pck_energy_span: the energy-span model of `landscape` = (registers of
+        the N entries, isTS flags) for n conditions in one launch.  Returns a
+        dict of the outputs named in `want` (pck_span_outputs' members):
+        tof, espan, eapp, dgrxn [n]; i_tdts, i_tdi [n] int32 landscape
+        indices; x_ts [nTi, n], x_int [nIj-1, n]; energy [N, n]."""
+        torch = self.torch
+        regs, is_ts = landscape
+        regs = [int(r) for r in regs]
+        N = len(regs)
+        if len(is_ts) != N:
+            raise ValueError('landscape has %d registers and %d isTS flags' % (N, len(is_ts)))
+        ls = L.Landscape()
+        ls.n_pts = N
+        for k in range(min(N, L.MAX_PES)):
+            ls.reg[k] = regs[k]
+            if is_ts[k]:
+                ls.ts_mask |= 1 << k
+        unknown = set(want) - set(self.SPAN_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown energy-span outputs %s' % sorted(unknown))
+        c, keep = self.conditions(n, T, p, desc)
+        n_ts = sum(1 for k in range(1, N - 1) if is_ts[k])
+        rows = dict(x_ts=n_ts, x_int=N - 2 - n_ts, energy=N)
+        out = {}
+        for k in self.SPAN_OUTPUTS:
+            if k not in want:
+                continue
+            if k in rows:
+                out[k] = torch.empty((max(rows[k], 1), max(n, 1)), dtype=torch.float64, device='cuda')
+            else:
+                out[k] = torch.empty(max(n, 1), dtype=torch.int32 if k.startswith('i_') else torch.float64,
+                                     device='cuda')
+        o = L.SpanOutputs()
+        for k, t in out.items():
+            setattr(o, k, _ptr(t))
+        o.ld_x = o.ld_e = max(n, 1)
+        L.check(self.lib.pck_energy_span(self.h, C.byref(c), C.byref(ls), C.byref(o), _stream(torch)))
+        return {k: (t[:max(rows[k], 0), :n] if k in rows else t[:n]) for k, t in out.items()}
+
     def rate_constants(self, n, T, p, desc=None):
         torch = self.torch
         c, keep = self.conditions(n, T, p, desc)

@@ -5,6 +5,7 @@ from __future__ import annotations
 import json
 import os
 
+from ..classes.energy import Energy
 from ..classes.reaction import Reaction, ReactionDerivedReaction, UserDefinedReaction
 from ..classes.reactor import CSTReactor, InfiniteDilutionReactor
 from ..classes.state import ScalingState, State
@@ -99,5 +100,9 @@ def read_from_input_file(input_path='input.json', base_system=None, base_dir=Non
     elif sim.reactions:
         raise RuntimeError('Cannot consider reactions without reactor. To use constant boundary conditions, '
                            'please specify InfiniteDilutionReactor.')
+    for pes, d in (pck.get('energy landscapes') or {}).items():     # load_input.py:154-163
+        minima = [[sim.states[s] for s in entry] for entry in d['minima']]
+        labels = d['labels'] if d.get('labels') else [i[0].name for i in minima]
+        sim.add_energy_landscape(Energy(name=pes, minima=minima, labels=labels))
     sim.names_to_indices()
     return sim

@@ -312,6 +312,69 @@ def save_state_energies(sim_system, csv_path=''):
     df.to_csv(csv_path + 'state_energies_%1.1fK_%1.1fbar.csv' % (T, p / bartoPa), index=False)
 
 
+# ----------------------------------------------------------------------------
+# energy landscapes (presets.py:323-375, 474-540)
+# ----------------------------------------------------------------------------
+def draw_energy_landscapes(sim_system, etype='free', eunits='eV', legend_location='upper right',
+                           show_labels=False, fig_path=None):
+    """presets.py:323-340 (plotting is out of scope: warns and is skipped)."""
+    _no_plots('draw_energy_landscapes', True)
+
+
+def compare_energy_landscapes(sim_systems, landscapes=None, etype='free', eunits='eV', legend_location=None,
+                              show_labels=False, fig_path=None, cmap=None):
+    """presets.py:501-540 (plotting is out of scope: warns and is skipped)."""
+    _no_plots('compare_energy_landscapes', True)
+
+
+def run_energy_span_temperatures(sim_system, temperatures, etype='free', save_results=False, csv_path=''):
+    """presets.py:343-375: the energy-span model of every landscape over
+    `temperatures` at params' pressure, one pck_energy_span launch per
+    landscape.  Prints the reference's block per temperature and, with
+    save_results, writes energy_span_summary_<k>.csv, energy_span_xTDTS_<k>.csv
+    and energy_span_xTDI_<k>.csv.  As in the reference, params['temperature']
+    is left at the last temperature."""
+    import pandas as pd
+    if save_results:
+        _mkdir(csv_path)
+    temps = list(temperatures)
+    for k, pes in sim_system.energy_landscapes.items():
+        print('Landscape %s:' % k)
+        print('-----------------')
+        esm = dict()
+        if temps:
+            r = pes.evaluate_batch(T=np.array([float(T) for T in temps]), p=sim_system.params['pressure'],
+                                   etype=etype)
+        for c, T in enumerate(temps):
+            sim_system.params['temperature'] = T
+            esm[T] = pes._report(r, c, T)
+        if save_results:
+            df = pd.DataFrame(data=[[T] + list(esm[T][0:4]) for T in temps],
+                              columns=['Temperature (K)', 'TOF (1/s)', 'Espan (eV)', 'TDTS', 'TDI'])
+            df.to_csv(csv_path + 'energy_span_summary_%s.csv' % k, index=False)
+            df = pd.DataFrame(data=[[T] + esm[T][4] for T in temps], columns=['Temperature (K)'] + esm[temps[0]][6])
+            df.to_csv(csv_path + 'energy_span_xTDTS_%s.csv' % k, index=False)
+            df = pd.DataFrame(data=[[T] + esm[T][5] for T in temps], columns=['Temperature (K)'] + esm[temps[0]][7])
+            df.to_csv(csv_path + 'energy_span_xTDI_%s.csv' % k, index=False)
+
+
+def save_pes_energies(sim_system, csv_path=''):
+    """presets.py:474-499: <landscape>_energy_landscape_<T>K_<p>bar.csv with
+    columns State, Free (eV), Electronic (eV) at params' T and p."""
+    import pandas as pd
+    _mkdir(csv_path)
+    T, p = sim_system.params['temperature'], sim_system.params['pressure']
+    evals = dict()
+    print('Saving state energies...')
+    for k, pes in sim_system.energy_landscapes.items():
+        pes.construct_energy_landscape(T=T, p=p, verbose=sim_system.params['verbose'])
+        for s in pes.energy_landscape['free'].keys():
+            evals[s] = [pes.energy_landscape['free'][s], pes.energy_landscape['electronic'][s]]
+        df = pd.DataFrame(data=[[pes.labels[s]] + evals[s] for s in evals.keys()],
+                          columns=['State', 'Free (eV)', 'Electronic (eV)'])
+        df.to_csv(csv_path + str(k) + '_energy_landscape_%1.1fK_%1.1fbar.csv' % (T, p / bartoPa), index=False)
+
+
 def get_tof_for_given_reactions(sim_system, tof_terms):
     """presets.py:585-597: sum of (r_fwd - r_rev) over tof_terms at the last
     transient state (sim_system.solution[-1]); the system's stored rates are
