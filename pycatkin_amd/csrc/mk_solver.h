@@ -80,7 +80,12 @@ __device__ double pck_lphase[8];
             for (int q = 0; q < 8; ++q) atomicAdd(&pck_lphase[q], lph[q]);             \
         }                                                                              \
     } while (0)
+// the phase accumulators handed to rodas_stages
+#define PCK_LPH_PARAMS , double (&lph)[8], const bool lph_on
+#define PCK_LPH_ARGS , lph, lph_on
 #else
+#define PCK_LPH_PARAMS
+#define PCK_LPH_ARGS
 #define PCK_LPH_DECL
 #define PCK_LPH(i, ...) __VA_ARGS__
 #define PCK_LPH_STEP() do {} while (0)
@@ -486,6 +491,67 @@ struct TrajOut {
     int64_t c;
 };
 
+// The six stages of one step on the factored W: u = y + a5. k + k5 (the new
+// state less the error estimate) and k6, plus the dense-output vectors for
+// TRAJ.  SWAPS = false is the hot instantiation: no lane of the wavefront
+// swapped a row in lu(), piv is not read, and the whole sequence is one basic
+// block.  SWAPS = true (cold) tests the wave-uniform `swaps` per column as
+// lu_solve does.
+template <bool SWAPS, bool TRAJ, class P, class K>
+__device__ __forceinline__ void rodas_stages(const P& p, const Lane<P::NS>& L, const K& k,
+                                             const double (&W)[P::NS][P::NS], const int (&piv)[P::NS], unsigned swaps,
+                                             const double (&y)[P::NS], const double (&F0)[P::NS], double ih, bool crows,
+                                             double (&u)[P::NS], double (&k6)[P::NS], double (&d2)[TRAJ ? P::NS : 1],
+                                             double (&d3)[TRAJ ? P::NS : 1] PCK_LPH_PARAMS) {
+    using namespace rodas4;
+    constexpr int NS = P::NS;
+    double k1[NS], k2[NS], k3[NS], k4[NS], k5[NS], fu[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) k1[i] = F0[i];
+    if (PCK_CONS_ROWS && crows) cons_zero(p, k1);
+    PCK_LPH(2, lu_solve_impl<NS, SWAPS>(W, piv, swaps, k1));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a21 * k1[i]);
+    PCK_LPH(3, rhs(p, L, k, u, fu));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) k2[i] = fu[i] + ih * (C21 * k1[i]));
+    if (PCK_CONS_ROWS && crows) cons_zero(p, k2);
+    PCK_LPH(2, lu_solve_impl<NS, SWAPS>(W, piv, swaps, k2));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a31 * k1[i] + a32 * k2[i]);
+    PCK_LPH(3, rhs(p, L, k, u, fu));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) k3[i] = fu[i] + ih * (C31 * k1[i] + C32 * k2[i]));
+    if (PCK_CONS_ROWS && crows) cons_zero(p, k3);
+    PCK_LPH(2, lu_solve_impl<NS, SWAPS>(W, piv, swaps, k3));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a41 * k1[i] + a42 * k2[i] + a43 * k3[i]);
+    PCK_LPH(3, rhs(p, L, k, u, fu));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) k4[i] = fu[i] + ih * (C41 * k1[i] + C42 * k2[i] + C43 * k3[i]));
+    if (PCK_CONS_ROWS && crows) cons_zero(p, k4);
+    PCK_LPH(2, lu_solve_impl<NS, SWAPS>(W, piv, swaps, k4));
+    // the one place the block is cut for the scheduler (max-ilp): without it
+    // the CSTR sweep, whose kernels sit at 255 VGPRs, ran 1.17-1.20 ms per
+    // 1e4 temperatures against 1.10-1.14 with it and 1.11-1.13 before the
+    // stage sequence was one block; the volcano line is the same either way
+    // (profiles/r7/lane_chain/)
+    __builtin_amdgcn_sched_barrier(0);
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a51 * k1[i] + a52 * k2[i] + a53 * k3[i] + a54 * k4[i]);
+    PCK_LPH(3, rhs(p, L, k, u, fu));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) k5[i] = fu[i] + ih * (C51 * k1[i] + C52 * k2[i] + C53 * k3[i] + C54 * k4[i]));
+    if (PCK_CONS_ROWS && crows) cons_zero(p, k5);
+    PCK_LPH(2, lu_solve_impl<NS, SWAPS>(W, piv, swaps, k5));
+    if constexpr (TRAJ) {
+        using namespace rodas4_dense;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            d2[i] = D21 * k1[i] + D22 * k2[i] + D23 * k3[i] + D24 * k4[i] + D25 * k5[i];
+            d3[i] = D3_K5_ONLY ? D35 * k5[i] : D31 * k1[i] + D32 * k2[i] + D33 * k3[i] + D34 * k4[i] + D35 * k5[i];
+        }
+    }
+    PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] += k5[i]);
+    PCK_LPH(3, rhs(p, L, k, u, fu));
+    PCK_LPH(4, for (int i = 0; i < NS; ++i)
+                   k6[i] = fu[i] + ih * (C61 * k1[i] + C62 * k2[i] + C63 * k3[i] + C64 * k4[i] + C65 * k5[i]));
+    if (PCK_CONS_ROWS && crows) cons_zero(p, k6);
+    PCK_LPH(2, lu_solve_impl<NS, SWAPS>(W, piv, swaps, k6));
+}
+
 template <bool TRAJ, class P, class K>
 __device__ PCK_LANE_INLINE int integrate(const P& p, const Lane<P::NS>& L, const K& k, double (&y)[P::NS], double t0,
                          double t_end, double rtol, double atol, int max_steps, int& nsteps, bool crows,
@@ -575,56 +641,26 @@ __device__ PCK_LANE_INLINE int integrate(const P& p, const Lane<P::NS>& L, const
             if (!(h > 2.220446049250313e-15 * fmax(fabs(t), 1e-300))) PCK_LRET(PCK_ST_STEPFAIL);
             continue;
         }
-        double k1[NS], k2[NS], k3[NS], k4[NS], k5[NS], u[NS], fu[NS];
-#pragma unroll
-        for (int i = 0; i < NS; ++i) k1[i] = F0[i];
-        if (PCK_CONS_ROWS && crows) cons_zero(p, k1);
-        PCK_LPH(2, lu_solve<NS>(W, piv, sw, k1));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a21 * k1[i]);
-        PCK_LPH(3, rhs(p, L, k, u, fu));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) k2[i] = fu[i] + ih * (C21 * k1[i]));
-        if (PCK_CONS_ROWS && crows) cons_zero(p, k2);
-        PCK_LPH(2, lu_solve<NS>(W, piv, sw, k2));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a31 * k1[i] + a32 * k2[i]);
-        PCK_LPH(3, rhs(p, L, k, u, fu));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) k3[i] = fu[i] + ih * (C31 * k1[i] + C32 * k2[i]));
-        if (PCK_CONS_ROWS && crows) cons_zero(p, k3);
-        PCK_LPH(2, lu_solve<NS>(W, piv, sw, k3));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a41 * k1[i] + a42 * k2[i] + a43 * k3[i]);
-        PCK_LPH(3, rhs(p, L, k, u, fu));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) k4[i] = fu[i] + ih * (C41 * k1[i] + C42 * k2[i] + C43 * k3[i]));
-        if (PCK_CONS_ROWS && crows) cons_zero(p, k4);
-        PCK_LPH(2, lu_solve<NS>(W, piv, sw, k4));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] = y[i] + a51 * k1[i] + a52 * k2[i] + a53 * k3[i] + a54 * k4[i]);
-        PCK_LPH(3, rhs(p, L, k, u, fu));
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) k5[i] = fu[i] + ih * (C51 * k1[i] + C52 * k2[i] + C53 * k3[i] + C54 * k4[i]));
-        if (PCK_CONS_ROWS && crows) cons_zero(p, k5);
-        PCK_LPH(2, lu_solve<NS>(W, piv, sw, k5));
+        // one branch on the wave-uniform `sw` for the whole stage sequence
+        // (lu_solve takes it once per solve): where no lane swapped, which is
+        // nearly every step, the six solves, the stage combinations and the
+        // six rhs are one basic block from here to the controller
+        double u[NS], k6[NS];
         double d2[TRAJ ? NS : 1], d3[TRAJ ? NS : 1];
-        if constexpr (TRAJ) {
-            using namespace rodas4_dense;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                d2[i] = D21 * k1[i] + D22 * k2[i] + D23 * k3[i] + D24 * k4[i] + D25 * k5[i];
-                d3[i] = D3_K5_ONLY ? D35 * k5[i] : D31 * k1[i] + D32 * k2[i] + D33 * k3[i] + D34 * k4[i] + D35 * k5[i];
-            }
-        }
-        PCK_LPH(4, for (int i = 0; i < NS; ++i) u[i] += k5[i]);
-        PCK_LPH(3, rhs(p, L, k, u, fu));
-        // k6 reuses k5's registers once k5 is folded into u
-        PCK_LPH(4, for (int i = 0; i < NS; ++i)
-                       k5[i] = fu[i] + ih * (C61 * k1[i] + C62 * k2[i] + C63 * k3[i] + C64 * k4[i] + C65 * k5[i]));
-        if (PCK_CONS_ROWS && crows) cons_zero(p, k5);
-        PCK_LPH(2, lu_solve<NS>(W, piv, sw, k5));
+        const unsigned swu = (unsigned)__builtin_amdgcn_readfirstlane((int)sw);
+        if (swu == 0u)
+            rodas_stages<false, TRAJ>(p, L, k, W, piv, 0u, y, F0, ih, crows, u, k6, d2, d3 PCK_LPH_ARGS);
+        else
+            rodas_stages<true, TRAJ>(p, L, k, W, piv, swu, y, F0, ih, crows, u, k6, d2, d3 PCK_LPH_ARGS);
         PCK_LPH_MARK();
         double s = 0.0, umin = INFINITY, usum = 0.0;
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
-            u[i] += k5[i];
+            u[i] += k6[i];
             usum += u[i];
             umin = fmin(umin, u[i]);
             const double sc = atol + rtol * fmax(fabs(y[i]), fabs(u[i]));
-            const double r = k5[i] * __builtin_amdgcn_rcp(sc);   // error weight: the v_rcp_f64 estimate suffices
+            const double r = k6[i] * __builtin_amdgcn_rcp(sc);   // error weight: the v_rcp_f64 estimate suffices
             s += r * r;
         }
         // one finiteness test for the step: a non-finite stage value makes u
@@ -635,8 +671,12 @@ __device__ PCK_LANE_INLINE int integrate(const P& p, const Lane<P::NS>& L, const
         // drives a component below -atol is rejected and retried at the
         // fraction of the step where that component reaches -atol
         const bool negv = PCK_POSITIVITY && umin < -atol;
-        const double fac = PCK_LANE_FAST ? step_factor_fast(q) : step_factor(q);
         if (q <= 1.0 && !negv) {
+            // the step-size factor (fp32 convert / log / exp chain) is needed
+            // only by the update of h at the end of this branch: started here,
+            // it overlaps the projection and rhs(y, F0) instead of standing
+            // between the error norm and the accept branch
+            const double hnew = h * fmin(PCK_FACMAX, fmax(0.2, (PCK_LANE_FAST ? step_factor_fast(q) : step_factor(q))));
             const double t_old = t;
             t = last ? t_end : t + h;
             double y_old[TRAJ ? NS : 1];
@@ -693,7 +733,7 @@ __device__ PCK_LANE_INLINE int integrate(const P& p, const Lane<P::NS>& L, const
                     if (y[i] < 0.0 && F0[i] < 0.0) { y[i] = 0.0; negf = true; }
                 if (__any(negf)) rhs(p, L, k, y, F0);
             }
-            h *= fmin(PCK_FACMAX, fmax(0.2, fac));
+            h = hnew;
         } else {
             double pf = 1.0;
             if (__any(negv)) {              // rare: one wave-uniform branch
@@ -704,7 +744,7 @@ __device__ PCK_LANE_INLINE int integrate(const P& p, const Lane<P::NS>& L, const
             if (q <= 1.0) {
                 h *= fmax(0.1, 0.9 * pf);
             } else {
-                h *= finite ? fmax(0.2, fac) : 0.25;
+                h *= finite ? fmax(0.2, (PCK_LANE_FAST ? step_factor_fast(q) : step_factor(q))) : 0.25;
                 // repeated catastrophic rejections: see mk_group.h grp_integrate
                 if (!(q < PCK_BLOWUP_Q) && h < 1e-4 * t && ++blowups > PCK_MAX_BLOWUPS) PCK_LRET(PCK_ST_STEPFAIL);
             }
