@@ -31,6 +31,8 @@
  *   pck_drc             <- System.degree_of_rate_control      old_system.py:490
  *   pck_energy_span     <- Energy.construct_energy_landscape  pycatkin/classes/energy.py:39
  *                          Energy.evaluate_energy_span_model  energy.py:238
+ *   pck_ensemble_noise  <- Uncertainty.get_correlated_state_noises pycatkin/classes/uncertainty.py:35
+ *   pck_ensemble_stats  <- Uncertainty.get_mean_property_value uncertainty.py:115 (np.mean / np.std over runs)
  *
  * All functions return 0 on success and a negative PCK_E_* code on failure;
  * pck_last_error() returns a message for the calling thread.  Device pointers
@@ -49,7 +51,7 @@
 extern "C" {
 #endif
 
-#define PCK_ABI_VERSION 7
+#define PCK_ABI_VERSION 8
 
 /* error codes */
 #define PCK_OK 0
@@ -334,6 +336,69 @@ typedef struct {
  * N-1 a TS, no TS or no intermediate among entries 1..N-2. */
 int pck_energy_span(const pck_network* net, const pck_conditions* cond, const pck_landscape* pes,
                     const pck_span_outputs* out, void* stream);
+
+/* ---- uncertainty ensemble (pycatkin/classes/uncertainty.py) -------------------
+ * An ensemble is n_rep blocks of B = n_runs + lead_zero consecutive conditions,
+ * one block per base condition (a temperature, say): run r of block c is
+ * condition c*B + lead_zero + r, so the runs of one base condition are
+ * contiguous (the 64 lanes of a wavefront share a temperature).  With
+ * lead_zero the first condition of each block is the unperturbed system (the
+ * reference's noisy_sys[0]).
+ *
+ * pck_ensemble_noise writes the [1 + n_ts][ld_desc] descriptor matrix that
+ * pck_conditions.desc reads (s_desc = 1) for the whole ensemble -- what
+ * Uncertainty.get_correlated_state_noises (uncertainty.py:35-65) draws per run
+ * with one np.random.normal and one np.random.uniform per transition state:
+ *   row 0     mu + sigma * z_r     the white noise every adsorbate of run r shares
+ *   row 1+k   row0 * u_{r,k}       transition state k < n_ts; u uniform in [0, 1),
+ *                                  independent of mu and sigma (the reference's
+ *                                  quirk, kept)
+ * and exactly 0 in every row of a block's lead column.  Columns beyond
+ * n_rep*B are not touched.  Every value is computed once per thread and
+ * written to each replica c.
+ *
+ * Generator: Philox4x32-10 (Salmon et al., SC'11), counter-based.  Key =
+ * (lo32(seed), hi32(seed)); counter = (lo32(run), hi32(run), j, 0) with
+ * run = run_first + r.  A 53-bit uniform from output words (w0, w1) is
+ * ((w0 * 2^32 + w1) >> 11) * 2^-53.  Block j = 0: (w0, w1) -> u1 taken as
+ * (k + 1) * 2^-53 (never 0), (w2, w3) -> u2, and the Box-Muller normal
+ * z = sqrt(-2 ln u1) * cos(2 pi u2) with 2 pi = 6.283185307179586.  Block
+ * j >= 1: (w0, w1) -> u of transition state 2(j-1), (w2, w3) -> u of
+ * 2(j-1)+1.  The noise of a run depends on (seed, run) alone -- not on n_runs,
+ * n_rep or the launch geometry -- so an ensemble is reproducible and a shard
+ * that starts at run_first draws the numbers the whole ensemble would.
+ *
+ * PCK_E_ARG: desc NULL, a negative size, lead_zero not 0 / 1,
+ * ld_desc < n_rep * B. */
+int pck_ensemble_noise(uint64_t seed, uint64_t run_first, int64_t n_runs, int64_t n_rep, int64_t n_ts,
+                       int lead_zero, double mu, double sigma, double* desc, int64_t ld_desc, void* stream);
+
+/* Outputs of pck_ensemble_stats (device pointers; any may be NULL), each
+ * [n_rows][ld_out] with ld_out >= n_rep. */
+typedef struct {
+    int32_t* count;              /* accepted columns */
+    double* mean;                /* NaN when count is 0 */
+    double* std;                 /* population standard deviation (np.std, ddof 0); NaN when count is 0 */
+    double* min;                 /* +inf when count is 0 */
+    double* max;                 /* -inf when count is 0 */
+    int64_t ld_out;
+} pck_ens_stats;
+
+/* Statistics over the runs of every base condition, for n_rows properties at
+ * once -- the np.mean / np.std of Uncertainty.get_mean_property_value
+ * (uncertainty.py:115-125).  For row q of v ([n_rows][ld_v]) and block c < n_rep
+ * the columns c*block + skip .. c*block + block - 1 are reduced (skip = 1 leaves
+ * out an ensemble's unperturbed lead column).  A column counts when its value
+ * is finite and, with status ([n_rep*block] PCK_ST_* codes, may be NULL), bit
+ * status[col] of ok_mask is set (a status outside 0..31 never counts).
+ * Per-thread Welford updates, then Chan's pairwise merge of (n, mean, M2)
+ * across the wavefront and across wavefronts, in an order fixed by `block`
+ * alone: no atomics, no sum of squares, bitwise the same from launch to launch.
+ * One workgroup per (row, block): 64 threads up to block = 256, 256 up to
+ * 16384, 1024 beyond.  PCK_E_ARG: v or out NULL, a negative size,
+ * ld_v < n_rep*block, ld_out < n_rep. */
+int pck_ensemble_stats(const double* v, int64_t ld_v, int64_t n_rows, const int32_t* status, uint32_t ok_mask,
+                       int64_t n_rep, int64_t block, int64_t skip, const pck_ens_stats* out, void* stream);
 
 #ifdef __cplusplus
 }

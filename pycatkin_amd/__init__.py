@@ -10,6 +10,7 @@ from .classes.reaction import Reaction, ReactionDerivedReaction, UserDefinedReac
 from .classes.reactor import CSTReactor, InfiniteDilutionReactor, Reactor  # noqa: F401
 from .classes.system import SteadyStateResults, System  # noqa: F401
 from .classes.solver import SolScore, SteadyStateSolver  # noqa: F401
+from .classes.uncertainty import Uncertainty  # noqa: F401
 from .functions.load_input import read_from_input_file  # noqa: F401
 
 __version__ = '0.1.0'

@@ -16,9 +16,10 @@ LIB_PATH = os.environ.get('PCK_LIB') or os.path.join(_HERE, 'libpycatkin_amd.so'
 # symbols declared in include/pycatkin_amd.h (checked by tests/test_capi.py)
 EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_network_destroy',
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
-            'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span')
+            'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
+            'pck_ensemble_stats')
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # header slot indices (must match the enums of include/pycatkin_amd.h)
 I_VERSION, I_NDESC, I_NTH, I_NREG, I_NRXN, I_NDYN, I_NFIX, I_NCONS, I_NTOF = range(9)
@@ -71,6 +72,11 @@ class SpanOutputs(C.Structure):
                 ('ld_x', C.c_int64), ('energy', C.c_void_p), ('ld_e', C.c_int64)]
 
 
+class EnsStats(C.Structure):
+    _fields_ = [('count', C.c_void_p), ('mean', C.c_void_p), ('std', C.c_void_p), ('min', C.c_void_p),
+                ('max', C.c_void_p), ('ld_out', C.c_int64)]
+
+
 _lib = None
 
 
@@ -106,6 +112,8 @@ def load():
     lib.pck_solve.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(Outputs), vp]
     lib.pck_drc.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
     lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
+    lib.pck_ensemble_noise.argtypes = [C.c_uint64, C.c_uint64, i64, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, vp]
+    lib.pck_ensemble_stats.argtypes = [vp, i64, i64, vp, C.c_uint32, i64, i64, i64, C.POINTER(EnsStats), vp]
     for name in EXPORTED:
         if name not in ('pck_last_error',):
             getattr(lib, name).restype = C.c_int

@@ -110,6 +110,14 @@ class System:
         self.rates = None
         self.rate_constants = None
         self._plans = {}
+        # Optional (both None: nothing changes).  descriptor_order: the
+        # descriptor names of every plan of this system, in device order (names
+        # no energy uses included); desc_defaults: {descriptor: value} used
+        # where a call passes no `desc`.  An uncertainty ensemble sets both
+        # (classes/uncertainty.py): its members share one plan and answer
+        # single-condition calls with their own noise values.
+        self.descriptor_order = None
+        self.desc_defaults = None
         self.set_parameters(times=times, start_state=start_state, inflow_state=inflow_state, T=T, p=p,
                             use_jacobian=use_jacobian, ode_solver=ode_solver, nsteps=nsteps, rtol=rtol, atol=atol,
                             xtol=xtol, ftol=ftol, verbose=verbose)
@@ -406,6 +414,8 @@ class System:
     # -- compilation -------------------------------------------------------------
     def plan(self, tof_terms=(), descriptors=None):
         from ..network import compile_system
+        if descriptors is None:
+            descriptors = getattr(self, 'descriptor_order', None)
         key = (tuple(tof_terms), tuple(descriptors) if descriptors else None, self.formulation, self.rate_model,
                self._energy_key())
         if key not in self._plans:
@@ -439,7 +449,18 @@ class System:
         T = self.params['temperature'] if T is None else T
         p = self.params['pressure'] if p is None else p
         d = None
-        if plan.descriptors:
+        if desc is None:
+            desc = getattr(self, 'desc_defaults', None)
+        if plan.descriptors and desc is not None and not isinstance(desc, dict):
+            # a [D, n] matrix in plan.descriptors order, host or device (an
+            # ensemble's noise matrix never leaves the device)
+            if any(k.startswith('@T:') for k in plan.descriptors):
+                raise ValueError('a descriptor matrix cannot fill temperature-keyed user energies; pass a dict')
+            if tuple(desc.shape) != (len(plan.descriptors), n):
+                raise ValueError('descriptor matrix has shape %s, expected (%d, %d)'
+                                 % (tuple(desc.shape), len(plan.descriptors), n))
+            d = desc
+        elif plan.descriptors:
             given = [k for k in plan.descriptors if not k.startswith('@T:')]
             if given and desc is None:
                 raise ValueError('network depends on descriptors %s' % given)
@@ -514,8 +535,10 @@ class System:
         (DESIGN.md "Round 6")."""
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
-        sizes = [T, p] + (list(desc.values()) if desc else [])
-        n = self._n(*sizes)
+        if desc is not None and not isinstance(desc, dict):
+            n = max(self._n(T, p), int(desc.shape[1]))
+        else:
+            n = self._n(*([T, p] + (list(desc.values()) if desc else [])))
         if y0 is not None and np.ndim(y0) == 2:
             n = max(n, np.shape(y0)[1])
         T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)

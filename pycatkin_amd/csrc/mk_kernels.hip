@@ -60,6 +60,10 @@ static int fail(int code, const char* fmt, const char* a = "", long long b = 0) 
     snprintf(g_err, sizeof(g_err), fmt, a, b);
     return code;
 }
+// the same message slot for the C-ABI entry points of other translation units (tu_ensemble.hip)
+namespace pck {
+int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+}  // namespace pck
 #define HIPCHK(x)                                                                  \
     do {                                                                           \
         hipError_t e_ = (x);                                                       \

@@ -341,3 +341,74 @@ def single_reaction_rate_constants(rxn, T, p):
     s.add_reactor(InfiniteDilutionReactor())
     kf, kr = s.rate_constants_batch(T=[float(T)], p=float(p))
     return float(kf[0, 0]), float(kr[0, 0])
+
+
+# -- uncertainty ensemble (csrc/tu_ensemble.hip) ---------------------------------
+def ensemble_noise(seed, n_runs, n_rep=1, n_ts=0, lead_zero=False, mu=0.0, sigma=0.01, run_first=0, out=None):
+    """pck_ensemble_noise: the [1 + n_ts, n_rep * (n_runs + lead_zero)] device
+    matrix of an ensemble's correlated energy noise (row 0 the adsorbates'
+    shared value, row 1+k transition state k's), in the block layout of
+    include/pycatkin_amd.h.  `out`: a contiguous float64 device matrix of at
+    least that many columns to write into (its other columns stay untouched)."""
+    torch = _torch()
+    lib = L.load()
+    B = int(n_runs) + int(bool(lead_zero))
+    if out is None:
+        out = torch.empty((1 + int(n_ts), max(int(n_rep) * B, 0)), dtype=torch.float64, device='cuda')
+    elif (out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2 or not out.is_contiguous()
+          or out.shape[0] < 1 + int(n_ts)):
+        raise ValueError('out must be a contiguous float64 device matrix of at least %d rows' % (1 + int(n_ts)))
+    L.check(lib.pck_ensemble_noise(int(seed) & (2 ** 64 - 1), int(run_first) & (2 ** 64 - 1), int(n_runs), int(n_rep),
+                                   int(n_ts), int(bool(lead_zero)), float(mu), float(sigma), _ptr(out),
+                                   int(out.shape[1]), _stream(torch)))
+    return out
+
+
+STAT_OUTPUTS = ('count', 'mean', 'std', 'min', 'max')
+
+
+def ensemble_stats(values, status=None, ok=(0, 4), block=None, skip=0, want=STAT_OUTPUTS):
+    """pck_ensemble_stats on a device matrix `values` [n_rows, n] (or [n]):
+    count / mean / population std / min / max over the columns
+    c*block + skip .. c*block + block - 1 of each of the n // block blocks
+    (block None: one block of n), counting the finite values whose `status`
+    ([n] int32 device tensor, optional) is one of `ok`.  Returns a dict of
+    device tensors [n_rows, n_rep] ([n_rep] for a 1-D input)."""
+    torch = _torch()
+    lib = L.load()
+    v = torch.as_tensor(values, dtype=torch.float64, device='cuda')
+    one_d = v.dim() == 1
+    if one_d:
+        v = v.reshape(1, -1)
+    if v.dim() != 2:
+        raise ValueError('values must be [n_rows, n] or [n]')
+    if v.stride(1) != 1 and v.shape[1] > 1 or (v.shape[0] > 1 and v.stride(0) < v.shape[1]):
+        v = v.contiguous()
+    n_rows, n = int(v.shape[0]), int(v.shape[1])
+    ld_v = int(v.stride(0)) if n_rows > 1 else max(n, 1)
+    block = n if block is None else int(block)
+    if block < 0 or skip < 0 or (block == 0 and n) or (block and n % block):
+        raise ValueError('%d columns are not whole blocks of %d' % (n, block))
+    n_rep = n // block if block else 0
+    st = None
+    if status is not None:
+        st = torch.as_tensor(status, dtype=torch.int32, device='cuda').reshape(-1).contiguous()
+        if st.numel() != n:
+            raise ValueError('status has %d entries for %d columns' % (st.numel(), n))
+    mask = 0
+    for s in ok:
+        if not 0 <= int(s) < 32:
+            raise ValueError('status codes to accept must lie in 0..31')
+        mask |= 1 << int(s)
+    unknown = set(want) - set(STAT_OUTPUTS)
+    if unknown:
+        raise ValueError('unknown statistics %s' % sorted(unknown))
+    out = {k: torch.empty((n_rows, max(n_rep, 1)), dtype=torch.int32 if k == 'count' else torch.float64,
+                          device='cuda') for k in STAT_OUTPUTS if k in want}
+    o = L.EnsStats()
+    for k, t in out.items():
+        setattr(o, k, _ptr(t))
+    o.ld_out = max(n_rep, 1)
+    L.check(lib.pck_ensemble_stats(_ptr(v), ld_v, n_rows, _ptr(st), mask, n_rep, block, int(skip), C.byref(o),
+                                   _stream(torch)))
+    return {k: (t[0, :n_rep] if one_d else t[:, :n_rep]) for k, t in out.items()}
