@@ -1162,10 +1162,12 @@ __device__ __forceinline__ double grp_solve64(const Grp<NSP>& x, const LU<NSP>& 
 template <int NSP, int G>
 __device__ __forceinline__ bool grp_lu(const Grp<NSP>& x, LU<NSP>& F) {
     if constexpr (G == 16 && NSP <= 16) return grp_lu16<NSP>(x, F);
-    // (exact-size hipRTC kernels only: the padded compiled-in fallback keeps
-    // the partial-pivoting form, whose unrolled interchanges at run-time NS
-    // took the split build's 64-lane unit past 10 minutes)
-    if constexpr (G == 64 && PCK_GRP_TPIV64 && PCK_GRP_EXACT) return grp_lu64<NSP>(x, F);
+    // (the padded compiled-in fallback too: with the partial-pivoting form
+    // below it rounded differently from the exact-size hipRTC kernel -- step
+    // counts off by up to 3 in ~1000 at 33 and 64 species,
+    // test_edge_exact_size_kernel_matches_padded; the unrolled interchanges
+    // at run-time NS make the split build's 64-lane unit its longest, ~10 min)
+    if constexpr (G == 64 && PCK_GRP_TPIV64) return grp_lu64<NSP>(x, F);
     bool fre = x.row;
     bool ok = true;
     F.step = NSP;
@@ -1226,7 +1228,7 @@ __device__ __forceinline__ bool grp_lu(const Grp<NSP>& x, LU<NSP>& F) {
 template <int NSP, int G>
 __device__ __forceinline__ double grp_solve(const Grp<NSP>& x, const LU<NSP>& F, double b) {
     if constexpr (G == 16 && NSP <= 16) return grp_solve16<NSP>(x, F, b);
-    if constexpr (G == 64 && PCK_GRP_TPIV64 && PCK_GRP_EXACT) return grp_solve64<NSP>(x, F, b);
+    if constexpr (G == 64 && PCK_GRP_TPIV64) return grp_solve64<NSP>(x, F, b);
 #pragma unroll
     for (int k = 0; k < NSP; ++k) {
         if (k < x.NS) {

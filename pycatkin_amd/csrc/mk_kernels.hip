@@ -31,6 +31,7 @@ struct pck_network {
     double* d_dp = nullptr;
     void* d_grp = nullptr;          // lane-group plan (mk_group.h): reaction records, species CSR of S
     int grp_ok = 0;                 // every reaction fits a record (<= 6 participants, exponents <= 31)
+    const char* grp_why = "";       // !grp_ok: the limit the network exceeds (the refusal's message)
     int grp_npmax = 0, grp_emax = 0;  // most participants of a reaction / largest exponent (hipRTC bounds)
     int grp_degmax = 0;               // largest row degree of the species CSR (hipRTC bound)
     GrpView gv;
@@ -454,6 +455,7 @@ extern "C" int pck_network_create(const int32_t* ip, int64_t n_ip, const double*
         std::vector<uint32_t> rx(4 * (size_t)(R > 0 ? R : 1), 0u);
         std::vector<int> npv(R > 0 ? R : 1, 0), dpv(R > 0 ? R : 1, 0), spv(6 * (size_t)(R > 0 ? R : 1), 0);
         net->grp_ok = (R <= 511) ? 1 : 0;
+        if (!net->grp_ok) net->grp_why = "more than 511 reactions";
         int ND = 0;
         for (int j = 0; j < R; ++j) {
             uint32_t w[3] = {0, 0, 0};
@@ -461,8 +463,14 @@ extern "C" int pck_network_create(const int32_t* ip, int64_t n_ip, const double*
             for (int i = 0; i < NS; ++i) {
                 const int ea = ip[oef + j * NS + i], eb = ip[oer + j * NS + i];
                 if (!(ea | eb)) continue;
-                if (n == PCK_GRP_MAX_PART || ea > PCK_GRP_MAX_EXP || eb > PCK_GRP_MAX_EXP) {
+                if (ea > PCK_GRP_MAX_EXP || eb > PCK_GRP_MAX_EXP) {
                     net->grp_ok = 0;
+                    net->grp_why = "a reaction has a stoichiometric exponent above 31";
+                    continue;
+                }
+                if (n == PCK_GRP_MAX_PART) {
+                    net->grp_ok = 0;
+                    net->grp_why = "a reaction has more than 6 dynamic participants";
                     continue;
                 }
                 net->grp_emax = std::max(net->grp_emax, std::max(ea, eb));
@@ -478,7 +486,10 @@ extern "C" int pck_network_create(const int32_t* ip, int64_t n_ip, const double*
             rx[4 * j + 0] = w[0]; rx[4 * j + 1] = w[1]; rx[4 * j + 2] = w[2];
             rx[4 * j + 3] = (uint32_t)ND - (uint32_t)n | ((uint32_t)n << 16);
         }
-        if (ND > 0x3fff) net->grp_ok = 0;
+        if (ND > 0x3fff) {
+            net->grp_ok = 0;
+            net->grp_why = "more than 16383 reaction participants";
+        }
         std::vector<int32_t> row(NS + 1, 0);
         std::vector<uint32_t> ent;
         for (int i = 0; i < NS; ++i) {
@@ -871,7 +882,7 @@ static bool grp_tables_pay(hipFunction_t f, size_t shm, size_t shm_tab) {
 
 static int launch_grp_rates(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
                             int64_t ld_k, const double* y, int64_t ld_y, double* out, int jac, hipStream_t s) {
-    if (!net->grp_ok) return fail(PCK_E_SIZE, "lane-group solver: a reaction has more than 6 dynamic participants%s", "");
+    if (!net->grp_ok) return fail(PCK_E_SIZE, "lane-group solver: %s", net->grp_why);
     const int NS = net->nv.NDYN;
     const int per = 64 / grp_g(NS);
     dim3 g((unsigned)((cond->n + per - 1) / per));
@@ -1273,7 +1284,7 @@ static int launch_solve(const pck_network* net, const pck_conditions* cond, cons
         a.screen_dist = a.root_dist * (prm->screen_margin > 0.0 ? prm->screen_margin : 0.1);
     }
     if (grp && !net->grp_ok)
-        return fail(PCK_E_SIZE, "lane-group solver: a reaction has more than 6 dynamic participants%s", "");
+        return fail(PCK_E_SIZE, "lane-group solver: %s", net->grp_why);
     GrpArgs ga;
     ga.M = drc_groups ? drc_groups : 1;
     ga.QB = 1;

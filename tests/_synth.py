@@ -31,6 +31,63 @@ def spec_of(net, desc, T=500.0):
     return dict(states=states, reactions=reactions, system=dict(times=[0.0, 1e4], T=T, p=1e5, start_state=start, rtol=1e-8, atol=1e-10), reactor=dict(kind='ID'))
 
 
+def edge_network(n_species, n_reactions, seed, n_gases=2, extra=()):
+    """A random one-site network of 3 <= n_species <= 64 dynamic species ('s'
+    and n_species - 1 adsorbates) in the plain-data layout of
+    synthetic_network (which needs >= 9 species), for the size and packing
+    limits of the solver kernels:
+
+      R0      G0 + s  <-> A0             molecular adsorption
+      R1      G1 + 2s <-> A_i + A_j      dissociative adsorption
+      R2..    A_i <-> A_k (i < k)        a chain that connects every adsorbate
+      next    `extra`: (reactants, products) name lists, inserted as surface
+              steps through a transition state (a repeated name is an
+              exponent: ['A2'] * 3 -> A2^3)
+      next    G_g + s <-> A_(g-1) for the gases past the first two (n_gases >
+              2: more ways on and off the surface)
+      rest    random X + Y <-> Z + s up to n_reactions (2 X <-> Z + s where
+              fewer than three adsorbates exist)
+
+    Energies as in synthetic_network: E0 + Ed . D per adsorbate, an intrinsic
+    barrier beta per reaction.  Its own RNG stream (default_rng(seed))."""
+    from pycatkin_amd.functions.synthetic import GASES
+    if not 3 <= n_species <= 64:
+        raise ValueError('edge_network: 3 <= n_species <= 64')
+    if not 2 <= n_gases <= len(GASES):
+        raise ValueError('edge_network: 2 <= n_gases <= %d' % len(GASES))
+    rng = np.random.default_rng(seed)
+    n_ads = n_species - 1
+    n_desc = 4
+    ads = ['A%d' % i for i in range(n_ads)]
+    gases = GASES[:n_gases]
+    i, j = rng.choice(n_ads, 2, replace=False)
+    rx = [('ads', [gases[0][0], 's'], [ads[0]]), ('ads', [gases[1][0], 's', 's'], [ads[i], ads[j]])]
+    for k in range(1, n_ads):
+        rx.append(('surf', [ads[int(rng.integers(k))]], [ads[k]]))
+    for reac, prod in extra:
+        rx.append(('surf', list(reac), list(prod)))
+    for g in range(2, n_gases):                                   # the further gases adsorb molecularly
+        rx.append(('ads', [gases[g][0], 's'], [ads[(g - 1) % n_ads]]))
+    if len(rx) > n_reactions:
+        raise ValueError('edge_network: %d species and %d extra reactions need >= %d reactions'
+                         % (n_species, len(extra), len(rx)))
+    while len(rx) < n_reactions:
+        if n_ads >= 3:
+            i, j, k = rng.choice(n_ads, 3, replace=False)
+        else:
+            i, k = rng.choice(n_ads, 2, replace=False)
+            j = i
+        rx.append(('surf', [ads[i], ads[j]], [ads[k], 's']))
+    E0 = rng.uniform(-1.2, 0.2, n_ads)
+    E0[0] = rng.uniform(-1.6, -0.8)                               # the adsorbed gas: ~ -1 eV vs. the gas
+    Ed = np.zeros((n_ads, n_desc))
+    for a in range(n_ads):                                        # 1-2 descriptors per adsorbate
+        for k in rng.choice(n_desc, int(rng.integers(1, 3)), replace=False):
+            Ed[a, k] = rng.uniform(0.3, 1.0)
+    beta = rng.uniform(0.4, 1.1, len(rx))
+    return dict(gases=gases, adsorbates=ads, reactions=rx, E0=E0, Ed=Ed, beta=beta, n_desc=n_desc)
+
+
 def oracle_point(desc):
     """Oracle transient (scipy BDF, the reference's solve_ivp path) + polished
     root at one descriptor vector of the synthetic network: (bdf_ok, regular,
