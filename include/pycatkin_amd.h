@@ -29,6 +29,8 @@
  *                          SteadyStateSolver.solve_ode        pycatkin/classes/solver.py:374
  *                          System.run_and_return_tof / activity old_system.py:470,517
  *   pck_drc             <- System.degree_of_rate_control      old_system.py:490
+ *   pck_drc_at          <- System.degree_of_rate_control      old_system.py:490 (its eps -> 0 limit,
+ *   pck_drc_adjoint        analytic: one steady solve + one adjoint solve instead of 2R+1 solves)
  *   pck_energy_span     <- Energy.construct_energy_landscape  pycatkin/classes/energy.py:39
  *                          Energy.evaluate_energy_span_model  energy.py:238
  *   pck_ensemble_noise  <- Uncertainty.get_correlated_state_noises pycatkin/classes/uncertainty.py:35
@@ -51,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PCK_ABI_VERSION 8
+#define PCK_ABI_VERSION 9
 
 /* error codes */
 #define PCK_OK 0
@@ -220,6 +222,9 @@ typedef struct {
  * two definitions of the answer and xi measures the rule switching, not rate
  * control.  xi / tof0 are still written. */
 #define PCK_ST_DRC_MIXED 6
+/* pck_drc_at / pck_drc_adjoint: the steady Jacobian (conservation rows in
+ * place) has a zero pivot or a non-finite factor; xi are NaN */
+#define PCK_ST_SENS_SINGULAR 7
 
 int pck_abi_version(void);
 const char* pck_last_error(void);
@@ -296,6 +301,39 @@ int pck_solve(const pck_network* net, const pck_conditions* cond,
 int pck_drc(const pck_network* net, const pck_conditions* cond,
             const pck_solve_params* prm, double* xi, int64_t ld_xi,
             double* tof0, int32_t* status, int32_t* nsteps, void* stream);
+
+/* Analytic degree of rate control (old_system.py:490 System.degree_of_rate_control
+ * in the limit eps -> 0) at given steady states y ([NS][ld_y]), kf / kr as
+ * pck_rate_constants gives them: xi[j][ld_xi] = d ln TOF / d ln k_j at fixed K_j for
+ * every active reaction, from one adjoint solve per condition,
+ *   A^T lambda = dTOF/dy,   xi_j = ([j in tof] net_j - lambda . dF/dln k_j) / TOF0,
+ * with F the steady equations as pck_solve's Newton polish poses them (the
+ * conservation laws in their pivot rows, a unit row for a species that is exactly 0
+ * with an exactly zero rate) and A = dF/dy.  Rates, Jacobian, factorisation and
+ * substitution are double-double: the matrix has condition ~1e16 at a steady state
+ * and fp64 leaves no digit of xi (DESIGN.md "Analytic DRC").  The states are taken
+ * as steady; nothing checks that they are.
+ * status_in (optional) gates the conditions: only PCK_ST_OK rows are computed, any
+ * other keeps its status and gets NaN xi.  tof0 (optional) is written for every
+ * condition.  status (optional): PCK_ST_NONFINITE for a zero or non-finite TOF0,
+ * PCK_ST_SENS_SINGULAR for a zero pivot or a non-finite factor (NaN xi both).
+ * Networks of up to PCK_MAX_DYN species and PCK_MAX_RXN reactions whose reactions
+ * fit the lane-group records (<= 6 dynamic participants, exponents <= 31), else
+ * PCK_E_SIZE; a network without TOF terms is PCK_E_ARG. */
+int pck_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+               int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+               double* xi, int64_t ld_xi, double* tof0, int32_t* status, void* stream);
+
+/* System.degree_of_rate_control(ss_solve=True) (old_system.py:490) in the limit
+ * eps -> 0: one steady solve (pck_solve with prm->newton = 1: rule, root_dist,
+ * screening, retry and wave order as given) and then pck_drc_at at its states.  Same
+ * outputs as pck_drc; prm->drc_eps and prm->want_activity are ignored.  A condition
+ * whose solve did not report a reached root (status != PCK_ST_OK) keeps that status:
+ * its xi are NaN, its tof0 the TOF of the state the solve reports.  nsteps
+ * (optional): the solve's steps.  PCK_E_ARG: prm->newton == 0 (a transient end has
+ * no implicit-function sensitivity), a trajectory request (t_out / n_out). */
+int pck_drc_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                    double* xi, int64_t ld_xi, double* tof0, int32_t* status, int32_t* nsteps, void* stream);
 
 /* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
  * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program

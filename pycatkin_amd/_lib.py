@@ -17,9 +17,9 @@ LIB_PATH = os.environ.get('PCK_LIB') or os.path.join(_HERE, 'libpycatkin_amd.so'
 EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_network_destroy',
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
             'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
-            'pck_ensemble_stats')
+            'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint')
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # header slot indices (must match the enums of include/pycatkin_amd.h)
 I_VERSION, I_NDESC, I_NTH, I_NREG, I_NRXN, I_NDYN, I_NFIX, I_NCONS, I_NTOF = range(9)
@@ -35,6 +35,7 @@ MAX_DYN, MAX_DYN_LANE, MAX_RXN, MAX_CONS, MAX_TOF = 64, 8, 256, 4, 16
 MAX_PES = 64
 PLAN_AUTO, PLAN_RUNTIME, PLAN_GROUP = 0, 1, 2
 ST_OK, ST_MAXSTEPS, ST_STEPFAIL, ST_NONFINITE, ST_NEWTON, ST_NEWTON_LOOSE, ST_DRC_MIXED = range(7)
+ST_SENS_SINGULAR = 7
 E_ARG, E_HIP, E_SIZE = -1, -2, -3
 
 
@@ -111,6 +112,8 @@ def load():
     lib.pck_reaction_rates.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp, i64, vp]
     lib.pck_solve.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(Outputs), vp]
     lib.pck_drc.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
+    lib.pck_drc_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]
+    lib.pck_drc_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
     lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
     lib.pck_ensemble_noise.argtypes = [C.c_uint64, C.c_uint64, i64, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, vp]
     lib.pck_ensemble_stats.argtypes = [vp, i64, i64, vp, C.c_uint32, i64, i64, i64, C.POINTER(EnsStats), vp]

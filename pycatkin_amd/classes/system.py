@@ -570,7 +570,7 @@ class System:
         return out
 
     def drc_batch(self, tof_terms, T=None, p=None, desc=None, eps=1.0e-3, steady=False, t_end=None, rtol=None,
-                  atol=None, max_steps=200000, y0=None, fix=None, inflow=None, screen='auto'):
+                  atol=None, max_steps=200000, y0=None, fix=None, inflow=None, screen='auto', method='fd'):
         """Degree of rate control of every reaction (old_system.py:490-515) for a batch.
         steady=True: each of the 2R+1 solves is a steady-state solve with
         solve_batch's rule (STEADY_TRANSIENT unless rtol / atol are given;
@@ -578,7 +578,24 @@ class System:
         transient end: the condition's status is then 4).  `screen`: as in
         solve_batch (each of the 2R+1 solves screened on its own).
 
-        Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0' and 'status'."""
+        method='fd' (the default) is the reference's central difference over
+        k_j (1 +- eps).  method='analytic' (steady=True only) takes one steady
+        solve and one adjoint solve of the steady Jacobian per condition
+        instead of 2R+1 solves (pck_drc_adjoint; DESIGN.md "Analytic DRC"):
+        xi_j = d ln TOF / d ln k_j at fixed K_j, the eps -> 0 limit of the
+        reference's definition, so it differs from an eps = 5e-2 run by
+        O(eps^2).  `eps` is ignored for 'analytic'.  A condition whose solve
+        did not report a reached root keeps that status (4, ...) and gets NaN
+        xi: a transient end has no implicit-function sensitivity; status 7: a
+        singular steady Jacobian.  `screen` then applies to the one solve.
+
+        Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0', 'status'
+        and 'nsteps'."""
+        if method not in ('fd', 'analytic'):
+            raise ValueError("method must be 'fd' or 'analytic', not %r" % (method,))
+        if method == 'analytic' and not steady:
+            raise ValueError("method='analytic' needs steady=True: the analytic degree of rate control is "
+                             "the sensitivity of a steady state")
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
         n = self._n(T, p, *(desc.values() if desc else []))
@@ -594,18 +611,43 @@ class System:
             if screen != 'auto':
                 raise ValueError("screen must be 'auto', None or an rtol")
             screen = SCREEN_RTOL if (steady and net.NDYN <= SCREEN_MAX_LANE_SPECIES) else None
-        r = net.drc(n, T, p, y0, d, fx, inflow, t0=times[0], t_end=times[-1] if t_end is None else t_end,
-                    rtol=self.params['rtol'] if rtol is None else rtol,
-                    atol=self.params['atol'] if atol is None else atol, max_steps=max_steps, newton=steady,
-                    drc_eps=eps, root_dist=ROOT_DIST if steady else 0.0,
-                    screen=(float(screen), SCREEN_MARGIN) if (steady and screen) else None)
+        run = net.drc_adjoint if method == 'analytic' else net.drc
+        r = run(n, T, p, y0, d, fx, inflow, t0=times[0], t_end=times[-1] if t_end is None else t_end,
+                rtol=self.params['rtol'] if rtol is None else rtol,
+                atol=self.params['atol'] if atol is None else atol, max_steps=max_steps, newton=steady,
+                drc_eps=eps, root_dist=ROOT_DIST if steady else 0.0,
+                screen=(float(screen), SCREEN_MARGIN) if (steady and screen) else None)
+        return self._drc_dict(plan, r, n)
+
+    def _drc_dict(self, plan, r, n):
         xi = r['xi'].cpu().numpy()
         out = {name: (xi[plan.reactions.index(name)] if name in plan.reactions else np.zeros(n))
                for name in plan.all_reactions}
         out['tof0'] = r['tof0'].cpu().numpy()
         out['status'] = r['status'].cpu().numpy()
-        out['nsteps'] = r['nsteps'].cpu().numpy()
+        if 'nsteps' in r:
+            out['nsteps'] = r['nsteps'].cpu().numpy()
         return out
+
+    def drc_at(self, tof_terms, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None, k=None):
+        """Analytic degree of rate control (drc_batch's method='analytic') at
+        given steady states Y [n_dynamic, n] in plan.dyn order -- solve_batch's
+        'y' -- without a solve (pck_drc_at).  The states are taken as steady.
+        status_in ([n], optional): only its 0 rows are computed, the others
+        keep their status and get NaN xi.  k = (kf, kr) [active reactions, n]:
+        rate constants to use instead of the network's own at (T, p, desc).
+        Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0' and 'status'."""
+        plan = self.plan(tuple(tof_terms), None)
+        net = self.device(tuple(tof_terms), None)
+        Y = np.asarray(Y, float)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.shape[0] != net.NDYN:
+            raise ValueError('Y has %d rows for %d dynamic species' % (Y.shape[0], net.NDYN))
+        n = Y.shape[1]
+        T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
+        kf, kr = net.rate_constants(n, T, p, d) if k is None else k
+        return self._drc_dict(plan, net.drc_at(n, T, p, Y, kf, kr, d, fx, inflow, status_in), n)
 
     # -- reference API (one condition) -------------------------------------------------
     def _full(self, plan, ydyn):
@@ -736,7 +778,8 @@ class System:
         if st != 0 and not (degenerate_ok and st in (4, 5, 6)):
             raise RuntimeError('%s: device solver status %d (1 max steps, 2 step failure, 3 non-finite, '
                                '4 no steady state reached: transient end, 5 the same with the first-pass '
-                               'transient, 6 a DRC mixing reached roots and transient ends)' % (what, st))
+                               'transient, 6 a DRC mixing reached roots and transient ends, 7 a singular steady '
+                               'Jacobian in the analytic DRC)' % (what, st))
 
     def reaction_terms(self, y):
         """old_system.py:202-225: rates (n_reactions, 2) at the full state y."""
@@ -779,13 +822,15 @@ class System:
         self._check(r['status'][0], 'activity', degenerate_ok=True)
         return float(r['tof'][0])
 
-    def degree_of_rate_control(self, tof_terms, ss_solve=False, eps=1.0e-3):
-        """old_system.py:490-515.  As the reference's (whose ss_solve path
+    def degree_of_rate_control(self, tof_terms, ss_solve=False, eps=1.0e-3, method='fd'):
+        """old_system.py:490-515.  method='analytic' (with ss_solve): drc_batch's
+        analytic route, eps ignored; a condition that has not reached a
+        steady state then has NaN xi.  As the reference's (whose ss_solve path
         returns wherever least_squares stops), a condition whose transient has
         not reached a steady state (status 4) still returns its xi: every TOF
         of the central difference is then that solve's answer by
         solve_batch's rule (a root reached, or the transient end at t_end)."""
-        r = self.drc_batch(tof_terms, T=[self.params['temperature']], eps=eps, steady=ss_solve)
+        r = self.drc_batch(tof_terms, T=[self.params['temperature']], eps=eps, steady=ss_solve, method=method)
         self._check(r['status'][0], 'degree_of_rate_control', degenerate_ok=True)
         if r['status'][0] == 6:
             import warnings

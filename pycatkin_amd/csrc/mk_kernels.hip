@@ -258,6 +258,7 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 }
 
 #include "mk_solver.h"
+#include "mk_sens.h"
 
 // The solver kernels are compiled in translation units of their own in the
 // product build (csrc/mk_inst.h, csrc/tu_*.hip): here they are only declared.
@@ -267,6 +268,9 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 #if PCK_SPLIT_TU
 #include "mk_inst.h"
 namespace pck {
+#define PCK_X(GG) PCK_DO_SENS(extern, GG)
+PCK_INST_SENS(PCK_X)
+#undef PCK_X
 #define PCK_X(N) PCK_DO_LANE_RT(extern, N)
 PCK_INST_LANE_RT(PCK_X)
 #undef PCK_X
@@ -1478,4 +1482,81 @@ extern "C" int pck_drc(const pck_network* net, const pck_conditions* cond, const
     // lane-group networks: one group per (condition, perturbation), combined after
     if (use_group(net, G)) return launch_solve(net, cond, prm, a, (hipStream_t)stream, kscr, 2 * R + 1);
     return launch_solve(net, cond, prm, a, (hipStream_t)stream, kscr);
+}
+
+// ----------------------------------------------------------------------------
+// analytic DRC (csrc/mk_sens.h)
+// ----------------------------------------------------------------------------
+static int launch_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                         int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in, double* xi,
+                         int64_t ld_xi, double* tof0, int32_t* status, hipStream_t s) {
+    const int64_t n = cond->n;
+    if (n == 0) return PCK_OK;
+    const int NS = net->nv.NDYN;
+    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "analytic DRC: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
+    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "analytic DRC: 1..%s%lld reactions", "", PCK_MAX_RXN);
+    if (!net->grp_ok) return fail(PCK_E_SIZE, "analytic DRC (record tables): %s", net->grp_why);
+    if (net->nv.NTOF < 1) return fail(PCK_E_ARG, "analytic DRC: the network has no TOF terms%s", "");
+    const int G = grp_g(NS), per = 64 / G;
+    const int64_t nb = (n + per - 1) / per;
+    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "analytic DRC: more than 2^31 - 1 workgroups%s", "");
+    const dim3 g((unsigned)nb);
+    const size_t shm = sens_lds_bytes(G);          // 16 / 32 / 64 KiB
+#define CALL(GG) hipLaunchKernelGGL((k_drc_adjoint<GG>), g, dim3(64), shm, s, net->nv, net->gv, cview(cond), kf, kr, ld_k, y, ld_y, status_in, xi, ld_xi, tof0, status)
+    if (G == 16) CALL(16);
+    else if (G == 32) CALL(32);
+    else CALL(64);
+#undef CALL
+    HIPCHK(hipGetLastError());
+    return PCK_OK;
+}
+
+// System.degree_of_rate_control (old_system.py:490) in the limit eps -> 0, at
+// given states.
+extern "C" int pck_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                          int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in, double* xi,
+                          int64_t ld_xi, double* tof0, int32_t* status, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    if (cond->n > 0 && (!kf || !kr || ld_k < cond->n)) return fail(PCK_E_ARG, "bad kf / kr%s", "");
+    if (cond->n > 0 && (!y || ld_y < cond->n)) return fail(PCK_E_ARG, "bad states y%s", "");
+    if (cond->n > 0 && (!xi || ld_xi < cond->n)) return fail(PCK_E_ARG, "bad xi output%s", "");
+    return launch_drc_at(net, cond, kf, kr, ld_k, y, ld_y, status_in, xi, ld_xi, tof0, status, (hipStream_t)stream);
+}
+
+// System.degree_of_rate_control (old_system.py:490) with ss_solve, in the limit
+// eps -> 0: one steady solve, then the adjoint solve at its states.
+extern "C" int pck_drc_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                               double* xi, int64_t ld_xi, double* tof0, int32_t* status, int32_t* nsteps,
+                               void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    rc = check_params(prm);
+    if (rc) return rc;
+    if (!prm->newton)
+        return fail(PCK_E_ARG, "pck_drc_adjoint needs newton = 1: a transient end has no implicit-function sensitivity%s", "");
+    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "pck_drc_adjoint takes no trajectory request (t_out)%s", "");
+    const int64_t n = cond->n;
+    if (n > 0 && (!xi || ld_xi < n)) return fail(PCK_E_ARG, "bad xi output%s", "");
+    if (n == 0) return PCK_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    const int NS = net->nv.NDYN, R = net->nv.NRXN;
+    // the solve's states and statuses: sized by the batch
+    StreamScratch yscr;
+    rc = salloc(yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    if (rc) return rc;
+    double* y = yscr.as<double>();
+    int32_t* st = (int32_t*)(y + (int64_t)NS * n);
+    pck_solve_params p = *prm;
+    p.want_activity = 0;
+    SolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = y; a.ld_y = n; a.tof = nullptr; a.status = st; a.nsteps = nsteps;
+    a.G = 1;
+    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
+    rc = launch_solve(net, cond, &p, a, s, kscr);
+    if (rc) return rc;
+    const double* kf = kscr.as<double>();
+    const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
+    return launch_drc_at(net, cond, kf, kr, n, y, n, st, xi, ld_xi, tof0, status, s);
 }

@@ -298,6 +298,43 @@ class DeviceNetwork:
                                  _stream(torch)))
         return dict(xi=xi[:self.NRXN], tof0=tof0, status=st, nsteps=ns)
 
+    def drc_at(self, n, T, p, y, kf, kr, desc=None, fixc=None, inflow=None, status_in=None):
+        """pck_drc_at: the analytic degree of rate control at the steady states
+        y [NDYN, n] (kf, kr [NRXN, n] as rate_constants gives them); status_in
+        ([n] int32, optional): only its 0 rows are computed.  Returns
+        dict(xi [NRXN, n], tof0 [n], status [n])."""
+        torch = self.torch
+        c, keep = self.conditions(n, T, p, desc, fixc, None, inflow)
+        y = torch.as_tensor(y, dtype=torch.float64, device='cuda').reshape(self.NDYN, n).contiguous()
+        kf = torch.as_tensor(kf, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        kr = torch.as_tensor(kr, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        si = None
+        if status_in is not None:
+            si = torch.as_tensor(status_in, dtype=torch.int32, device='cuda').reshape(-1).contiguous()
+            if si.numel() != n:
+                raise ValueError('status_in has %d entries for %d conditions' % (si.numel(), n))
+        xi = torch.zeros((max(self.NRXN, 1), n), dtype=torch.float64, device='cuda')
+        tof0 = torch.empty(n, dtype=torch.float64, device='cuda')
+        st = torch.empty(n, dtype=torch.int32, device='cuda')
+        L.check(self.lib.pck_drc_at(self.h, C.byref(c), _ptr(kf), _ptr(kr), n, _ptr(y), n, _ptr(si), _ptr(xi), n,
+                                    _ptr(tof0), _ptr(st), _stream(torch)))
+        return dict(xi=xi[:self.NRXN], tof0=tof0, status=st)
+
+    def drc_adjoint(self, n, T, p, y0, desc=None, fixc=None, inflow=None, **kw):
+        """pck_drc_adjoint: one steady solve (kw as for solve; newton=True is
+        required) and the analytic degree of rate control at its states.
+        Returns what drc returns."""
+        torch = self.torch
+        c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)
+        prm = self.params(**kw)
+        xi = torch.zeros((max(self.NRXN, 1), n), dtype=torch.float64, device='cuda')
+        tof0 = torch.empty(n, dtype=torch.float64, device='cuda')
+        st = torch.empty(n, dtype=torch.int32, device='cuda')
+        ns = torch.empty(n, dtype=torch.int32, device='cuda')
+        L.check(self.lib.pck_drc_adjoint(self.h, C.byref(c), C.byref(prm), _ptr(xi), n, _ptr(tof0), _ptr(st),
+                                         _ptr(ns), _stream(torch)))
+        return dict(xi=xi[:self.NRXN], tof0=tof0, status=st, nsteps=ns)
+
 
 _form_cache = {}
 
