@@ -31,6 +31,8 @@
  *   pck_drc             <- System.degree_of_rate_control      old_system.py:490
  *   pck_drc_at          <- System.degree_of_rate_control      old_system.py:490 (its eps -> 0 limit,
  *   pck_drc_adjoint        analytic: one steady solve + one adjoint solve instead of 2R+1 solves)
+ *   pck_sens_at         <- (none: the reference has no reaction orders, apparent activation
+ *   pck_sens_adjoint       energy or per-direction sensitivities; the same adjoint solve gives them)
  *   pck_energy_span     <- Energy.construct_energy_landscape  pycatkin/classes/energy.py:39
  *                          Energy.evaluate_energy_span_model  energy.py:238
  *   pck_ensemble_noise  <- Uncertainty.get_correlated_state_noises pycatkin/classes/uncertainty.py:35
@@ -53,7 +55,7 @@
 extern "C" {
 #endif
 
-#define PCK_ABI_VERSION 9
+#define PCK_ABI_VERSION 10
 
 /* error codes */
 #define PCK_OK 0
@@ -225,6 +227,10 @@ typedef struct {
 /* pck_drc_at / pck_drc_adjoint: the steady Jacobian (conservation rows in
  * place) has a zero pivot or a non-finite factor; xi are NaN */
 #define PCK_ST_SENS_SINGULAR 7
+/* pck_sens_at / pck_sens_adjoint: max_j max(rf_j, rr_j) / |TOF| is so large that
+ * double-double no longer resolves the per-direction sensitivities (err > err_max):
+ * sf, sr, order, order_in and dir are NaN; xi and tof0 are written and reliable */
+#define PCK_ST_SENS_PRECISION 8
 
 int pck_abi_version(void);
 const char* pck_last_error(void);
@@ -334,6 +340,70 @@ int pck_drc_at(const pck_network* net, const pck_conditions* cond, const double*
  * no implicit-function sensitivity), a trajectory request (t_out / n_out). */
 int pck_drc_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
                     double* xi, int64_t ld_xi, double* tof0, int32_t* status, int32_t* nsteps, void* stream);
+
+/* Adjoint sensitivities of the TOF at steady states: what pck_drc_at's adjoint
+ * vector lambda gives beyond xi.  For any parameter theta of the steady equations
+ *   d TOF / d theta = dTOF/dtheta|_y - lambda . dF/dtheta|_y,
+ * and with s_j = [j in tof] - sum_i lambda_i w_i S_ij (the bracket of xi_j; w_i the row
+ * scale, 0 on a replaced row) and rf_j / rr_j the forward / reverse rate of reaction j
+ * every output below is a sum of s_j rf_j and s_j rr_j.  Device pointers, each
+ * optional (NULL: not wanted); [rows][ld] with ld >= n. */
+typedef struct {
+    double* xi; int64_t ld_xi;        /* [NRXN][ld_xi]  d ln TOF / d ln k_j at fixed K_j = (rf_j - rr_j) s_j / TOF,
+                                       *   bitwise what pck_drc_at writes */
+    double* sf; double* sr;           /* [NRXN][ld_s]   d ln TOF / d ln kf_j = rf_j s_j / TOF and
+                                       *   d ln TOF / d ln kr_j = -rr_j s_j / TOF, each at the other fixed
+                                       *   (sf + sr = xi) */
+    int64_t ld_s;
+    double* order; int64_t ld_order;  /* [NFIX][ld_order]  reaction order d ln TOF / d ln c_q in the
+                                       *   concentration of every fixed species q:
+                                       *   sum_j s_j (ef_jq rf_j - er_jq rr_j) / TOF, ef / er its exponents */
+    double* order_in; int64_t ld_in;  /* [NDYN][ld_in]  d ln TOF / d ln in_i in the inflow of a dynamic
+                                       *   species with a flow term fl (in - y) (the CSTR's gas rows):
+                                       *   -lambda_i fl_i in_i / TOF; 0 for a row without a flow term or a
+                                       *   replaced row */
+    double* dir; int64_t ld_dir;      /* [nd][ld_dir]  the directions of pck_sens_dirs */
+    double* err;                      /* [n]  the guard's bound, 2^-98 max_j max(rf_j, rr_j) / |TOF| */
+    double* tof0;                     /* [n]  the TOF at the given states (every condition) */
+    int32_t* status;                  /* [n]  PCK_ST_* */
+} pck_sens_out;
+
+/* User directions: dir[m] = sum_j (a_mj sf_j + c_mj sr_j), the derivative of ln TOF
+ * along d ln kf_j = a_mj, d ln kr_j = c_mj, summed in double-double and rounded once.
+ * a = c = 1 gives sum_j xi_j; a_j = d ln kf_j / dT, c_j = d ln kr_j / dT gives
+ * d ln TOF / dT at fixed gas composition (the apparent activation energy over R T^2);
+ * a state-energy or thermodynamic-DRC direction is one row.  Device pointers. */
+typedef struct {
+    int64_t nd;                       /* number of directions (0: none) */
+    const double* a; const double* c; /* [nd][NRXN][ld]: entry (m, j) of condition i at m * stride + j * ld + i */
+    int64_t ld, stride;               /* ld >= n; stride >= NRXN * ld */
+} pck_sens_dirs;
+
+/* The adjoint sensitivities at given steady states y ([NS][ld_y]), kf / kr as
+ * pck_rate_constants gives them: pck_drc_at's assembly, factorisation and adjoint solve
+ * (double-double throughout), then the outputs of pck_sens_out.  dirs may be NULL.
+ * The guard: sf_j = rf_j s_j / TOF needs s_j to an absolute accuracy of TOF / rf_j,
+ * which xi_j = (rf_j - rr_j) s_j / TOF does not, and double-double carries s_j to about
+ * 2^-98.  err = 2^-98 max_j max(rf_j, rr_j) / |TOF| bounds the error of every output
+ * but xi; with err_max > 0, a condition with err > err_max gets NaN sf, sr, order,
+ * order_in and dir and PCK_ST_SENS_PRECISION, its xi, tof0 and err as always
+ * (err_max <= 0: no guard; 1e-9 keeps every regular steady state of the test networks
+ * with |TOF| > 1e-40).  The bound is safe, not tight.
+ * status_in, PCK_ST_NONFINITE and PCK_ST_SENS_SINGULAR as pck_drc_at: NaN in every
+ * output but tof0.  Sizes and refusals as pck_drc_at; PCK_E_ARG also for a leading
+ * dimension below n or directions without a / c / dir. */
+int pck_sens_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+                const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out, void* stream);
+
+/* One steady solve (pck_solve with prm->newton = 1, as pck_drc_adjoint) and then
+ * pck_sens_at at its states, with the solve's own rate constants.  dirs are per
+ * condition of `cond`.  nsteps (optional): the solve's steps.  A condition whose solve
+ * did not report a reached root keeps that status and gets NaN outputs (tof0: the TOF
+ * of the state the solve reports).  PCK_E_ARG: prm->newton == 0, a trajectory request. */
+int pck_sens_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                     const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out, int32_t* nsteps,
+                     void* stream);
 
 /* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
  * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program

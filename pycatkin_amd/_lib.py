@@ -17,9 +17,9 @@ LIB_PATH = os.environ.get('PCK_LIB') or os.path.join(_HERE, 'libpycatkin_amd.so'
 EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_network_destroy',
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
             'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
-            'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint')
+            'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint', 'pck_sens_at', 'pck_sens_adjoint')
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # header slot indices (must match the enums of include/pycatkin_amd.h)
 I_VERSION, I_NDESC, I_NTH, I_NREG, I_NRXN, I_NDYN, I_NFIX, I_NCONS, I_NTOF = range(9)
@@ -36,6 +36,7 @@ MAX_PES = 64
 PLAN_AUTO, PLAN_RUNTIME, PLAN_GROUP = 0, 1, 2
 ST_OK, ST_MAXSTEPS, ST_STEPFAIL, ST_NONFINITE, ST_NEWTON, ST_NEWTON_LOOSE, ST_DRC_MIXED = range(7)
 ST_SENS_SINGULAR = 7
+ST_SENS_PRECISION = 8
 E_ARG, E_HIP, E_SIZE = -1, -2, -3
 
 
@@ -78,6 +79,17 @@ class EnsStats(C.Structure):
                 ('max', C.c_void_p), ('ld_out', C.c_int64)]
 
 
+class SensOut(C.Structure):
+    _fields_ = [('xi', C.c_void_p), ('ld_xi', C.c_int64), ('sf', C.c_void_p), ('sr', C.c_void_p), ('ld_s', C.c_int64),
+                ('order', C.c_void_p), ('ld_order', C.c_int64), ('order_in', C.c_void_p), ('ld_in', C.c_int64),
+                ('dir', C.c_void_p), ('ld_dir', C.c_int64), ('err', C.c_void_p), ('tof0', C.c_void_p),
+                ('status', C.c_void_p)]
+
+
+class SensDirs(C.Structure):
+    _fields_ = [('nd', C.c_int64), ('a', C.c_void_p), ('c', C.c_void_p), ('ld', C.c_int64), ('stride', C.c_int64)]
+
+
 _lib = None
 
 
@@ -114,6 +126,10 @@ def load():
     lib.pck_drc.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
     lib.pck_drc_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.pck_drc_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
+    lib.pck_sens_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, C.POINTER(SensDirs), C.c_double,
+                                C.POINTER(SensOut), vp]
+    lib.pck_sens_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(SensDirs), C.c_double,
+                                     C.POINTER(SensOut), vp, vp]
     lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
     lib.pck_ensemble_noise.argtypes = [C.c_uint64, C.c_uint64, i64, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, vp]
     lib.pck_ensemble_stats.argtypes = [vp, i64, i64, vp, C.c_uint32, i64, i64, i64, C.POINTER(EnsStats), vp]

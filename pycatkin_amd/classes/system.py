@@ -14,6 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from ..constants.physical_constants import R, bartoPa, eVtokJ, h, kB
+from .. import _lib as _L
 from ..energy import TKEYED, LinearForm
 from .reaction import Reaction
 from .reactor import InfiniteDilutionReactor, Reactor
@@ -533,6 +534,8 @@ class System:
         (the volcano grid) and is overhead where they do not: a 262 144-
         temperature CSTR sweep takes 1.71 ms with it off against 2.36 ms
         (DESIGN.md "Round 6")."""
+        if wave_order not in ('auto', 'on', 'off'):
+            raise ValueError("wave_order must be 'auto', 'on' or 'off', not %r" % (wave_order,))
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
         if desc is not None and not isinstance(desc, dict):
@@ -648,6 +651,162 @@ class System:
         T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
         kf, kr = net.rate_constants(n, T, p, d) if k is None else k
         return self._drc_dict(plan, net.drc_at(n, T, p, Y, kf, kr, d, fx, inflow, status_in), n)
+
+    # -- adjoint sensitivities (DESIGN.md "Adjoint sensitivities") ------------------------
+    def _dlnk_dT(self, net, n, T, p, d):
+        """(d ln kf / dT, d ln kr / dT) [NRXN, n] on the device: the 5-point
+        central stencil of the network's rate constants at h = 1e-3 T (four
+        launches), 0 where a rate constant is 0."""
+        torch = net.torch
+        if torch.is_tensor(T):
+            Tn = T.to(dtype=torch.float64, device='cuda').reshape(-1).expand(n)
+        else:
+            Tn = torch.as_tensor(np.broadcast_to(np.asarray(T, float), (n,)).copy(), dtype=torch.float64, device='cuda')
+        hh = 1.0e-3 * Tn
+        acc = [0.0, 0.0]
+        live = [None, None]
+        for m, w in ((-2.0, 1.0), (-1.0, -8.0), (1.0, 8.0), (2.0, -1.0)):
+            k = net.rate_constants(n, Tn + m * hh, p, d)
+            for q in (0, 1):
+                acc[q] = acc[q] + w * torch.log(k[q])
+                live[q] = k[q] > 0.0
+        zero = torch.zeros((), dtype=torch.float64, device='cuda')
+        return tuple(torch.where(live[q], acc[q] / (12.0 * hh), zero) for q in (0, 1))
+
+    def _eapp_check(self, plan):
+        if any(k.startswith('@T:') for k in plan.descriptors):
+            raise ValueError('apparent activation energy: the plan has temperature-keyed user energies (%s); a '
+                             'tabulated energy has no temperature derivative'
+                             % ', '.join(k for k in plan.descriptors if k.startswith('@T:')))
+        ns = len(plan.dyn)
+        off = int(plan.ip[_L.I_HDR + _L.D_DYN])
+        dyn = np.asarray(plan.dp[off: off + 4 * ns]).reshape(ns, 4)
+        if np.any(dyn[:, 2] != 0.0):
+            raise ValueError('apparent activation energy: the row scale of this reactor depends on T (the CSTR\'s '
+                             'gas rows); its term is not implemented')
+
+    def dlnk_dT_batch(self, T=None, p=None, desc=None):
+        """(a, c) = (d ln kf / dT, d ln kr / dT), [active reactions, n] device
+        tensors, at fixed p and descriptors: the direction whose sensitivity
+        is d ln TOF / dT (sensitivity_batch's eapp).  5-point central stencil
+        of the rate constants at h = 1e-3 T; 0 where a rate constant is 0
+        (irreversible steps).  Refuses temperature-keyed ('@T:') plans."""
+        plan = self.plan((), None)
+        net = self.device((), None)
+        if any(k.startswith('@T:') for k in plan.descriptors):
+            raise ValueError('dlnk_dT_batch: a temperature-keyed user energy has no temperature derivative')
+        n = self._n(T, p, *(desc or {}).values()) if desc else self._n(T, p)
+        T, p, d, _, _, _ = self._inputs(net, plan, n, T, p, desc, None, None, None)
+        return self._dlnk_dT(net, n, T, p, d)
+
+    def _sens_dict(self, plan, r, n, T, eapp):
+        """The device dict of sens_at / sens_adjoint by name, on the host."""
+        h = {k: v.cpu().numpy() for k, v in r.items()}
+        out = {}
+        for key in ('xi', 'sf', 'sr'):
+            out[key] = {name: (h[key][plan.reactions.index(name)] if name in plan.reactions else np.zeros(n))
+                        for name in plan.all_reactions}
+        out['order'] = {name: h['order'][q] for q, name in enumerate(plan.fix)}
+        off = int(plan.ip[_L.I_HDR + _L.D_DYN])
+        flow = np.asarray(plan.dp[off: off + 4 * len(plan.dyn)]).reshape(len(plan.dyn), 4)[:, 3]
+        out['order_inflow'] = {name: h['order_in'][i] for i, name in enumerate(plan.dyn) if flow[i] != 0.0}
+        nd = h['dir'].shape[0] - (1 if eapp else 0)
+        out['dir'] = h['dir'][:nd]
+        if eapp:
+            Tn = np.broadcast_to(np.asarray(T, float), (n,))
+            out['eapp'] = R * Tn * Tn * h['dir'][nd]
+        for key in ('tof0', 'status', 'err', 'nsteps'):
+            if key in h:
+                out[key] = h[key]
+        return out
+
+    def _sens_directions(self, net, plan, n, T, p, d, directions, eapp):
+        """User directions [ND, R, n] (or None) plus, last, d ln k / dT for eapp."""
+        torch = net.torch
+        a = c = None
+        if directions is not None:
+            a, c = (torch.as_tensor(x, dtype=torch.float64, device='cuda') for x in directions)
+            if a.dim() == 2:
+                a, c = a[None], c[None]
+            if tuple(a.shape) != (a.shape[0], net.NRXN, n) or tuple(c.shape) != tuple(a.shape):
+                raise ValueError('directions: expected two [ND, %d, %d] arrays in plan.reactions order, got %s and %s'
+                                 % (net.NRXN, n, tuple(a.shape), tuple(c.shape)))
+        if eapp:
+            ta, tc = self._dlnk_dT(net, n, T, p, d)
+            a = ta[None] if a is None else torch.cat([a, ta[None]])
+            c = tc[None] if c is None else torch.cat([c, tc[None]])
+        return None if a is None else (a, c)
+
+    def sensitivity_at(self, tof_terms, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None, k=None,
+                       directions=None, err_max=1.0e-9, eapp=False):
+        """First-order sensitivities of the TOF at given steady states Y
+        [n_dynamic, n] (plan.dyn order), from the adjoint solve of the analytic
+        degree of rate control (pck_sens_at) -- arguments as drc_at.  Returns
+        a dict:
+          'xi', 'sf', 'sr'  {reaction: [n]}: d ln TOF / d ln k_j at fixed K_j, and
+                            d ln TOF / d ln kf_j, d ln TOF / d ln kr_j separately
+                            (sf + sr = xi; ghost reactions 0)
+          'order'           {fixed species: [n]}: d ln TOF / d ln (its concentration)
+          'order_inflow'    {dynamic species with a flow term: [n]}: the order in
+                            its inflow concentration (the CSTR)
+          'dir'             [ND, n]: sum_j (a_mj sf_j + c_mj sr_j) for directions =
+                            (a, c), [ND, active reactions, n] each in
+                            plan.reactions order (d ln kf, d ln kr)
+          'eapp'            [n] J/mol with eapp=True: R T^2 d ln TOF / dT at fixed
+                            p, gas composition and descriptors (dlnk_dT_batch)
+          'tof0', 'status', 'err' [n].
+        A condition whose err = 2^-98 max rate / |TOF| exceeds err_max has
+        status 8 and NaN everywhere but 'xi', 'tof0', 'err': double-double no
+        longer resolves the per-direction numbers there (err_max <= 0: no
+        guard)."""
+        plan = self.plan(tuple(tof_terms), None)
+        if eapp:
+            self._eapp_check(plan)
+        net = self.device(tuple(tof_terms), None)
+        Y = np.asarray(Y, float)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.shape[0] != net.NDYN:
+            raise ValueError('Y has %d rows for %d dynamic species' % (Y.shape[0], net.NDYN))
+        n = Y.shape[1]
+        T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
+        dirs = self._sens_directions(net, plan, n, T, p, d, directions, eapp)
+        kf, kr = net.rate_constants(n, T, p, d) if k is None else k
+        r = net.sens_at(n, T, p, Y, kf, kr, d, fx, inflow, status_in, directions=dirs, err_max=err_max)
+        return self._sens_dict(plan, r, n, T, eapp)
+
+    def sensitivity_batch(self, tof_terms, T=None, p=None, desc=None, steady=True, t_end=None, rtol=None, atol=None,
+                          max_steps=200000, y0=None, fix=None, inflow=None, screen='auto', directions=None,
+                          eapp=False, err_max=1.0e-9):
+        """One steady solve per condition (drc_batch's rule and options) and
+        sensitivity_at at its states, in two launches (pck_sens_adjoint).
+        Returns sensitivity_at's dict plus 'nsteps'.  A condition whose solve
+        did not report a reached root keeps that status (4, ...) and gets NaN."""
+        if not steady:
+            raise ValueError('sensitivity_batch needs steady=True: the adjoint sensitivities are those of a '
+                             'steady state')
+        plan = self.plan(tuple(tof_terms), None)
+        if eapp:
+            self._eapp_check(plan)
+        net = self.device(tuple(tof_terms), None)
+        n = self._n(T, p, *(desc.values() if desc else []))
+        for a in (y0, fix, inflow):
+            if a is not None and np.ndim(a) == 2:
+                n = max(n, np.shape(a)[1])
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)
+        dirs = self._sens_directions(net, plan, n, T, p, d, directions, eapp)
+        times = self.params['times'] or [0.0, 1.0e4]
+        rtol = STEADY_TRANSIENT[0] if rtol is None else rtol
+        atol = STEADY_TRANSIENT[1] if atol is None else atol
+        if isinstance(screen, str):
+            if screen != 'auto':
+                raise ValueError("screen must be 'auto', None or an rtol")
+            screen = SCREEN_RTOL if net.NDYN <= SCREEN_MAX_LANE_SPECIES else None
+        r = net.sens_adjoint(n, T, p, y0, d, fx, inflow, directions=dirs, err_max=err_max, t0=times[0],
+                             t_end=times[-1] if t_end is None else t_end, rtol=rtol, atol=atol, max_steps=max_steps,
+                             newton=True, root_dist=ROOT_DIST,
+                             screen=(float(screen), SCREEN_MARGIN) if screen else None)
+        return self._sens_dict(plan, r, n, T, eapp)
 
     # -- reference API (one condition) -------------------------------------------------
     def _full(self, plan, ydyn):
@@ -779,7 +938,8 @@ class System:
             raise RuntimeError('%s: device solver status %d (1 max steps, 2 step failure, 3 non-finite, '
                                '4 no steady state reached: transient end, 5 the same with the first-pass '
                                'transient, 6 a DRC mixing reached roots and transient ends, 7 a singular steady '
-                               'Jacobian in the analytic DRC)' % (what, st))
+                               'Jacobian in the analytic DRC, 8 rates too large against the TOF for the '
+                               'double-double adjoint sensitivities)' % (what, st))
 
     def reaction_terms(self, y):
         """old_system.py:202-225: rates (n_reactions, 2) at the full state y."""
@@ -838,6 +998,28 @@ class System:
                           '(some reached a root, some report the transient end at t_end): the central '
                           'differences mix the two and xi measures the rule switching (status 6)')
         return {k: float(r[k][0]) for k in self.reactions}
+
+    def reaction_orders(self, tof_terms, ss_solve=True):
+        """{fixed species: d ln TOF / d ln (its pressure)} plus the inflow orders of
+        a CSTR's gas species, at the System's temperature and pressure
+        (sensitivity_batch; modelled on degree_of_rate_control(method='analytic')).
+        Raises where the condition is flagged (no steady state reached, a
+        singular Jacobian, status 8: not resolvable in double-double)."""
+        if not ss_solve:
+            raise ValueError('reaction_orders needs ss_solve=True: the orders are those of a steady state')
+        r = self.sensitivity_batch(tof_terms, T=[self.params['temperature']])
+        self._check(r['status'][0], 'reaction_orders')
+        out = {k: float(v[0]) for k, v in r['order'].items()}
+        out.update({k: float(v[0]) for k, v in r['order_inflow'].items()})
+        return out
+
+    def apparent_activation_energy(self, tof_terms):
+        """R T^2 d ln TOF / dT (J/mol) of the steady state at the System's
+        temperature and pressure, at fixed gas composition
+        (sensitivity_batch(eapp=True)).  Raises where the condition is flagged."""
+        r = self.sensitivity_batch(tof_terms, T=[self.params['temperature']], eapp=True)
+        self._check(r['status'][0], 'apparent_activation_energy')
+        return float(r['eapp'][0])
 
     # patched-API steady state (system.py:566-639)
     def find_steady_state(self, max_iters=30, y0=None, method=None):

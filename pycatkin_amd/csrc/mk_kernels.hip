@@ -1511,6 +1511,96 @@ static int launch_drc_at(const pck_network* net, const pck_conditions* cond, con
     return PCK_OK;
 }
 
+// the adjoint sensitivities (csrc/mk_sens.h: k_sens_adjoint); the checks of launch_drc_at
+static int launch_sens_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                          int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+                          const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out, hipStream_t s) {
+    const int64_t n = cond->n;
+    if (!out) return fail(PCK_E_ARG, "adjoint sensitivities: no outputs%s", "");
+    if (n == 0) return PCK_OK;
+    const int NS = net->nv.NDYN;
+    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "adjoint sensitivities: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
+    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "adjoint sensitivities: 1..%s%lld reactions", "", PCK_MAX_RXN);
+    if (!net->grp_ok) return fail(PCK_E_SIZE, "adjoint sensitivities (record tables): %s", net->grp_why);
+    if (net->nv.NTOF < 1) return fail(PCK_E_ARG, "adjoint sensitivities: the network has no TOF terms%s", "");
+    if ((out->xi && out->ld_xi < n) || ((out->sf || out->sr) && out->ld_s < n) || (out->order && out->ld_order < n) ||
+        (out->order_in && out->ld_in < n))
+        return fail(PCK_E_ARG, "adjoint sensitivities: a leading dimension of pck_sens_out is below n%s", "");
+    SensExt ex;
+    memset(&ex, 0, sizeof(ex));
+    ex.sf = out->sf; ex.sr = out->sr; ex.ld_s = out->ld_s;
+    ex.order = out->order; ex.ld_o = out->ld_order;
+    ex.order_in = out->order_in; ex.ld_oi = out->ld_in;
+    ex.err = out->err;
+    ex.err_max = err_max;
+    if (dirs && dirs->nd > 0) {
+        if (dirs->nd > 0x7fffffffLL || !dirs->a || !dirs->c || !out->dir || dirs->ld < n || out->ld_dir < n ||
+            dirs->stride < (int64_t)net->nv.NRXN * dirs->ld)
+            return fail(PCK_E_ARG, "adjoint sensitivities: bad directions (a, c, dir, ld >= n, stride >= NRXN * ld)%s", "");
+        ex.a = dirs->a; ex.c = dirs->c; ex.ld_ac = dirs->ld; ex.s_ac = dirs->stride; ex.nd = (int)dirs->nd;
+        ex.dir = out->dir; ex.ld_dir = out->ld_dir;
+    }
+    const int G = grp_g(NS), per = 64 / G;
+    const int64_t nb = (n + per - 1) / per;
+    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "adjoint sensitivities: more than 2^31 - 1 workgroups%s", "");
+    const dim3 g((unsigned)nb);
+    const size_t shm = sens_lds_bytes(G);          // 16 / 32 / 64 KiB
+#define CALL(GG) hipLaunchKernelGGL((k_sens_adjoint<GG>), g, dim3(64), shm, s, net->nv, net->gv, cview(cond), kf, kr, ld_k, y, ld_y, status_in, out->xi, out->ld_xi, out->tof0, out->status, ex)
+    if (G == 16) CALL(16);
+    else if (G == 32) CALL(32);
+    else CALL(64);
+#undef CALL
+    HIPCHK(hipGetLastError());
+    return PCK_OK;
+}
+
+// d TOF / d theta = dTOF/dtheta|_y - lambda . dF/dtheta|_y at given states: reaction
+// orders, per-direction sensitivities, user directions (the reference has none of them).
+extern "C" int pck_sens_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                           int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+                           const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    if (cond->n > 0 && (!kf || !kr || ld_k < cond->n)) return fail(PCK_E_ARG, "bad kf / kr%s", "");
+    if (cond->n > 0 && (!y || ld_y < cond->n)) return fail(PCK_E_ARG, "bad states y%s", "");
+    return launch_sens_at(net, cond, kf, kr, ld_k, y, ld_y, status_in, dirs, err_max, out, (hipStream_t)stream);
+}
+
+// One steady solve, then pck_sens_at at its states (pck_drc_adjoint's shape).
+extern "C" int pck_sens_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                                const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out,
+                                int32_t* nsteps, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    rc = check_params(prm);
+    if (rc) return rc;
+    if (!prm->newton)
+        return fail(PCK_E_ARG, "pck_sens_adjoint needs newton = 1: a transient end has no implicit-function sensitivity%s", "");
+    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "pck_sens_adjoint takes no trajectory request (t_out)%s", "");
+    if (!out) return fail(PCK_E_ARG, "adjoint sensitivities: no outputs%s", "");
+    const int64_t n = cond->n;
+    if (n == 0) return PCK_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    const int NS = net->nv.NDYN, R = net->nv.NRXN;
+    StreamScratch yscr;                            // the solve's states and statuses
+    rc = salloc(yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    if (rc) return rc;
+    double* y = yscr.as<double>();
+    int32_t* st = (int32_t*)(y + (int64_t)NS * n);
+    pck_solve_params p = *prm;
+    p.want_activity = 0;
+    SolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = y; a.ld_y = n; a.tof = nullptr; a.status = st; a.nsteps = nsteps;
+    a.G = 1;
+    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
+    rc = launch_solve(net, cond, &p, a, s, kscr);
+    if (rc) return rc;
+    const double* kf = kscr.as<double>();
+    const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
+    return launch_sens_at(net, cond, kf, kr, n, y, n, st, dirs, err_max, out, s);
+}
+
 // System.degree_of_rate_control (old_system.py:490) in the limit eps -> 0, at
 // given states.
 extern "C" int pck_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,

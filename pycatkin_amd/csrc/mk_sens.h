@@ -78,7 +78,10 @@ __device__ __forceinline__ void sens_keff(const NetView& nv, const SensIn& in, i
 // it), or its derivative in the state of participant k0: that factor's power
 // is lowered by one and multiplied by exponent and concentration factor --
 // never a division by a concentration, so y_q = 0 is an ordinary case
-__device__ __forceinline__ dd sens_rate(const NetView& nv, const SensIn& in, const uint4& rec, dd a, dd b, int k0) {
+//
+// sens_sides leaves the forward side in a and the reverse side in b;
+// sens_rate is their difference
+__device__ __forceinline__ void sens_sides(const NetView& nv, const SensIn& in, const uint4& rec, dd& a, dd& b, int k0) {
 #pragma unroll
     for (int k = 0; k < PCK_GRP_MAX_PART; ++k) {
         const int f = rx_field(rec, k);
@@ -97,6 +100,9 @@ __device__ __forceinline__ dd sens_rate(const NetView& nv, const SensIn& in, con
             a = b = dd_of(0.0);
         }
     }
+}
+__device__ __forceinline__ dd sens_rate(const NetView& nv, const SensIn& in, const uint4& rec, dd a, dd b, int k0) {
+    sens_sides(nv, in, rec, a, b, k0);
     return dd_sub(a, b);
 }
 
@@ -106,14 +112,52 @@ __device__ __forceinline__ dd gbcast_dd(dd v, int src) { return {gbcast<G>(v.hi,
 // LDS bytes of a 64-thread block: 64 / G matrices of G x G double-doubles
 __host__ __device__ constexpr size_t sens_lds_bytes(int G) { return (size_t)(64 / G) * G * G * sizeof(dd); }
 
-// xi[j][ld_xi] for every active reaction, tof0 and status per condition.
-// status_in (optional): only PCK_ST_OK conditions are computed, the others
-// keep their status and get NaN xi; tof0 is written for every condition.
+// What k_sens_adjoint writes beyond xi (pck_sens_out / pck_sens_dirs of the
+// C-ABI): every pointer optional.  With s_j = cnt_j - sum_i lambda_i w_i S_ij
+// the bracket of xi_j, rf_j / rr_j the forward / reverse rate of reaction j:
+//   sf[j], sr[j]     rf_j s_j / TOF, -rr_j s_j / TOF                  [R][ld_s]
+//   order[q]         sum_j s_j (ef_jq rf_j - er_jq rr_j) / TOF        [NFIX][ld_o]
+//   order_in[i]      -lambda_i fl_i in_i / TOF (0 without a flow term) [NDYN][ld_oi]
+//   dir[m]           sum_j s_j (rf_j a_mj - rr_j c_mj) / TOF          [nd][ld_dir]
+//   err              2^-98 max_j max(rf_j, rr_j) / |TOF|              [n]
+struct SensExt {
+    double* sf; double* sr; int64_t ld_s;
+    double* order; int64_t ld_o;
+    double* order_in; int64_t ld_oi;
+    const double* a; const double* c; int64_t ld_ac, s_ac;   // [nd][R][ld_ac], direction m at m * s_ac
+    int nd;
+    double* dir; int64_t ld_dir;
+    double* err;
+    double err_max;                                          // <= 0: no guard
+};
+#define PCK_SENS_ERR_UNIT 0x1p-98
+
+// NaN into every output of SensExt of condition c, one lane per entry
 template <int G>
-__global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, CondView cv, const double* kf,
-                                                    const double* kr, int64_t ld_k, const double* yin, int64_t ld_y,
-                                                    const int32_t* status_in, double* xi, int64_t ld_xi,
-                                                    double* tof0, int32_t* status) {
+__device__ __forceinline__ void sens_ext_nan(const NetView& nv, const SensExt& ex, int64_t c, int gl, bool with_err) {
+    const double NaN = __builtin_nan("");
+    for (int j = gl; j < nv.NRXN; j += G) {
+        if (ex.sf) ex.sf[j * ex.ld_s + c] = NaN;
+        if (ex.sr) ex.sr[j * ex.ld_s + c] = NaN;
+    }
+    if (ex.order)
+        for (int q = gl; q < nv.NFIX; q += G) ex.order[q * ex.ld_o + c] = NaN;
+    if (ex.order_in && gl < nv.NDYN) ex.order_in[gl * ex.ld_oi + c] = NaN;
+    if (ex.dir)
+        for (int m = gl; m < ex.nd; m += G) ex.dir[m * ex.ld_dir + c] = NaN;
+    if (with_err && ex.err && gl == 0) ex.err[c] = NaN;
+}
+
+// The body of k_drc_adjoint (EXT = false: xi[j][ld_xi] for every active
+// reaction, tof0 and status per condition) and of k_sens_adjoint (EXT = true:
+// the outputs of SensExt as well, xi optional).  status_in (optional): only
+// PCK_ST_OK conditions are computed, the others keep their status and get NaN
+// outputs; tof0 is written for every condition.
+template <int G, bool EXT>
+__device__ __forceinline__ void sens_body(const NetView& nv, const GrpView& gv, const CondView& cv, const double* kf,
+                                          const double* kr, int64_t ld_k, const double* yin, int64_t ld_y,
+                                          const int32_t* status_in, double* xi, int64_t ld_xi, double* tof0,
+                                          int32_t* status, const SensExt& ex) {
     extern __shared__ double lds[];
     const int grp = threadIdx.x / G, gl = threadIdx.x % G;
     const int64_t c = (int64_t)blockIdx.x * (64 / G) + grp;
@@ -138,7 +182,9 @@ __global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, Cond
     int st = status_in ? status_in[c] : PCK_ST_OK;
     if (st == PCK_ST_OK && !(isfinite(tofd) && tofd != 0.0)) st = PCK_ST_NONFINITE;
     if (st != PCK_ST_OK) {                         // group-uniform
-        for (int j = gl; j < R; j += G) xi[j * ld_xi + c] = NaN;
+        if (!EXT || xi)
+            for (int j = gl; j < R; j += G) xi[j * ld_xi + c] = NaN;
+        if constexpr (EXT) sens_ext_nan<G>(nv, ex, c, gl, true);
         if (gl == 0 && status) status[c] = st;
         return;
     }
@@ -146,6 +192,7 @@ __global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, Cond
     for (int q = 0; q < G; ++q) M[q * G + gl] = dd_of(0.0);
     // row gl of A into column gl of M, and the row's rate f
     double yi = 0.0, rs = 0.0;
+    double flin = 0.0;                             // EXT: the inflow in_i of a row with a flow term
     bool pv = false;
     int law = -1;
     dd f = dd_of(0.0);
@@ -171,6 +218,7 @@ __global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, Cond
         if (fl != 0.0) {                            // the CSTR flow term fl (in - y)
             const double yin_i = cv.inflow ? cv.inflow[gl * cv.ld_in + c * cv.s_in] : 0.0;
             f = dd_add(f, dd_mul(two_sum(yin_i, -yi), fl));
+            if constexpr (EXT) flin = yin_i;
             M[gl * G + gl] = dd_add(M[gl * G + gl], dd_of(-fl));
         }
         for (int l = 0; l < nv.NCONS; ++l)
@@ -252,7 +300,9 @@ __global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, Cond
     const double lsum = lam.hi + lam.lo;
     ok = ok && gmin<G>((!row || isfinite(lsum)) ? 1.0 : 0.0) > 0.0;
     if (!ok) {
-        for (int j = gl; j < R; j += G) xi[j * ld_xi + c] = NaN;
+        if (!EXT || xi)
+            for (int j = gl; j < R; j += G) xi[j * ld_xi + c] = NaN;
+        if constexpr (EXT) sens_ext_nan<G>(nv, ex, c, gl, true);
         if (gl == 0 && status) status[c] = PCK_ST_SENS_SINGULAR;
         return;
     }
@@ -260,11 +310,10 @@ __global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, Cond
     wsync();
     if (row) M[gl] = dd_mul(dd_scale(lam, dc), wi);
     wsync();
-    // xi_j = net_j ([j in tof] - sum_i lambda_i w_i S_ij) / TOF, lane per reaction
-    for (int j = gl; j < R; j += G) {
-        dd a, b;
-        sens_keff(nv, in, j, a, b);
-        const dd net = sens_rate(nv, in, gv.rx[j], a, b, -1);
+    // the bracket s_j = [j in tof] - sum_i lambda_i w_i S_ij and the two sides of reaction j
+    auto terms = [&](int j, dd& rf, dd& rr) -> dd {
+        sens_keff(nv, in, j, rf, rr);
+        sens_sides(nv, in, gv.rx[j], rf, rr, -1);
         int cnt = 0;
         for (int t = 0; t < nv.NTOF; ++t) cnt += (nv.tof[t] == j);
         dd s = dd_of((double)cnt);
@@ -272,16 +321,107 @@ __global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, Cond
             const double sv = nv.S[i * R + j];
             if (sv != 0.0) s = dd_sub(s, dd_mul(M[i], sv));
         }
-        const dd x = dd_div(dd_mul(net, s), tof);
-        xi[j * ld_xi + c] = x.hi + x.lo;
+        return s;
+    };
+    // xi_j = net_j s_j / TOF, lane per reaction
+    double rmax = 0.0;
+    for (int j = gl; j < R; j += G) {
+        dd rf, rr;
+        const dd s = terms(j, rf, rr);
+        if (!EXT || xi) {
+            const dd x = dd_div(dd_mul(dd_sub(rf, rr), s), tof);
+            xi[j * ld_xi + c] = x.hi + x.lo;
+        }
+        if constexpr (EXT) {
+            const double m = fmax(fabs(rf.hi), fabs(rr.hi));
+            rmax = (m != m) ? INFINITY : fmax(rmax, m);
+        }
+    }
+    if constexpr (EXT) {
+        // the guard: sf_j needs s_j to TOF / rf_j absolute, and the double-double
+        // lambda gives it to ~2^-98 (DESIGN.md "Adjoint sensitivities")
+        const double err = PCK_SENS_ERR_UNIT * gmax<G>(rmax) / fabs(tofd);
+        if (gl == 0 && ex.err) ex.err[c] = err;
+        if (ex.err_max > 0.0 && !(err <= ex.err_max)) {          // group-uniform
+            sens_ext_nan<G>(nv, ex, c, gl, false);
+            if (gl == 0 && status) status[c] = PCK_ST_SENS_PRECISION;
+            return;
+        }
+        if (ex.sf || ex.sr) {
+            for (int j = gl; j < R; j += G) {
+                dd rf, rr;
+                const dd s = terms(j, rf, rr);
+                const dd xf = dd_div(dd_mul(rf, s), tof), xr = dd_div(dd_mul(rr, s), tof);
+                if (ex.sf) ex.sf[j * ex.ld_s + c] = xf.hi + xf.lo;
+                if (ex.sr) ex.sr[j * ex.ld_s + c] = -(xr.hi + xr.lo);
+            }
+        }
+        // reaction orders in the fixed species: the group's lanes share the sum over j
+        if (ex.order) {
+            for (int q = 0; q < nv.NFIX; ++q) {
+                dd acc = dd_of(0.0);
+                for (int j = gl; j < R; j += G) {
+                    const int ea = nv.foldf[j * nv.NFIX + q], eb = nv.foldr[j * nv.NFIX + q];
+                    if (!(ea | eb)) continue;
+                    dd rf, rr;
+                    const dd s = terms(j, rf, rr);
+                    acc = dd_add(acc, dd_mul(s, dd_sub(dd_mul(rf, (double)ea), dd_mul(rr, (double)eb))));
+                }
+                const dd x = dd_div(gsum_dd<G>(acc), tof);
+                if (gl == 0) ex.order[q * ex.ld_o + c] = x.hi + x.lo;
+            }
+        }
+        // ... and in the inflow of a species with a flow term (not scaled by the row scale)
+        if (ex.order_in && row) {
+            const double fl = nv.dyn[4 * gl + 3];
+            dd x = dd_of(0.0);
+            if (fl != 0.0 && !(pv || pin)) x = dd_div(dd_mul(dd_mul(dd_scale(lam, dc), -fl), flin), tof);
+            ex.order_in[gl * ex.ld_oi + c] = x.hi + x.lo;
+        }
+        // user directions (d ln kf, d ln kr)
+        if (ex.dir) {
+            for (int m = 0; m < ex.nd; ++m) {
+                const double* am = ex.a + m * ex.s_ac;
+                const double* cm = ex.c + m * ex.s_ac;
+                dd acc = dd_of(0.0);
+                for (int j = gl; j < R; j += G) {
+                    dd rf, rr;
+                    const dd s = terms(j, rf, rr);
+                    acc = dd_add(acc, dd_mul(s, dd_sub(dd_mul(rf, am[j * ex.ld_ac + c]), dd_mul(rr, cm[j * ex.ld_ac + c]))));
+                }
+                const dd x = dd_div(gsum_dd<G>(acc), tof);
+                if (gl == 0) ex.dir[m * ex.ld_dir + c] = x.hi + x.lo;
+            }
+        }
     }
     if (gl == 0 && status) status[c] = PCK_ST_OK;
+}
+
+// xi[j][ld_xi] for every active reaction, tof0 and status per condition.
+template <int G>
+__global__ void __launch_bounds__(64) k_drc_adjoint(NetView nv, GrpView gv, CondView cv, const double* kf,
+                                                    const double* kr, int64_t ld_k, const double* yin, int64_t ld_y,
+                                                    const int32_t* status_in, double* xi, int64_t ld_xi,
+                                                    double* tof0, int32_t* status) {
+    sens_body<G, false>(nv, gv, cv, kf, kr, ld_k, yin, ld_y, status_in, xi, ld_xi, tof0, status, SensExt{});
+}
+
+// The same adjoint solve spent on every first-order sensitivity of the TOF
+// (SensExt): per-direction sensitivities, reaction orders, user directions.
+template <int G>
+__global__ void __launch_bounds__(64) k_sens_adjoint(NetView nv, GrpView gv, CondView cv, const double* kf,
+                                                     const double* kr, int64_t ld_k, const double* yin, int64_t ld_y,
+                                                     const int32_t* status_in, double* xi, int64_t ld_xi,
+                                                     double* tof0, int32_t* status, SensExt ex) {
+    sens_body<G, true>(nv, gv, cv, kf, kr, ld_k, yin, ld_y, status_in, xi, ld_xi, tof0, status, ex);
 }
 
 #define PCK_SIG_SENS                                                                                          \
     NetView, GrpView, CondView, const double*, const double*, int64_t, const double*, int64_t, const int32_t*, \
         double*, int64_t, double*, int32_t*
 #define PCK_INST_SENS(X) X(16) X(32) X(64)
-#define PCK_DO_SENS(EXT, GG) EXT template __global__ void k_drc_adjoint<GG>(PCK_SIG_SENS);
+#define PCK_DO_SENS(EXT, GG)                                         \
+    EXT template __global__ void k_drc_adjoint<GG>(PCK_SIG_SENS); \
+    EXT template __global__ void k_sens_adjoint<GG>(PCK_SIG_SENS, SensExt);
 
 }  // namespace pck

@@ -335,6 +335,76 @@ class DeviceNetwork:
                                          _ptr(ns), _stream(torch)))
         return dict(xi=xi[:self.NRXN], tof0=tof0, status=st, nsteps=ns)
 
+    def _sens_io(self, n, directions):
+        """(pck_sens_out, pck_sens_dirs or None, output tensors, tensors to keep
+        alive) of sens_at / sens_adjoint."""
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device='cuda')
+        keep, dirs, nd = [], None, 0
+        if directions is not None:
+            a, c = (torch.as_tensor(x, **f64) for x in directions)
+            if a.dim() == 2:
+                a, c = a[None], c[None]
+            nd = int(a.shape[0])
+            if tuple(a.shape) != (nd, self.NRXN, n) or tuple(c.shape) != tuple(a.shape):
+                raise ValueError('directions: expected two [ND, %d, %d] arrays, got %s and %s'
+                                 % (self.NRXN, n, tuple(a.shape), tuple(c.shape)))
+            a, c = a.contiguous(), c.contiguous()
+            keep += [a, c]
+            dirs = L.SensDirs()
+            dirs.nd, dirs.a, dirs.c, dirs.ld, dirs.stride = nd, _ptr(a), _ptr(c), n, self.NRXN * n
+        t = dict(xi=torch.zeros((max(self.NRXN, 1), n), **f64), sf=torch.zeros((max(self.NRXN, 1), n), **f64),
+                 sr=torch.zeros((max(self.NRXN, 1), n), **f64), order=torch.zeros((max(self.NFIX, 1), n), **f64),
+                 order_in=torch.zeros((max(self.NDYN, 1), n), **f64), dir=torch.zeros((max(nd, 1), n), **f64),
+                 err=torch.empty(n, **f64), tof0=torch.empty(n, **f64),
+                 status=torch.empty(n, dtype=torch.int32, device='cuda'))
+        o = L.SensOut()
+        o.xi, o.ld_xi, o.sf, o.sr, o.ld_s = _ptr(t['xi']), n, _ptr(t['sf']), _ptr(t['sr']), n
+        o.order, o.ld_order, o.order_in, o.ld_in = _ptr(t['order']), n, _ptr(t['order_in']), n
+        o.dir, o.ld_dir = _ptr(t['dir']), n
+        o.err, o.tof0, o.status = _ptr(t['err']), _ptr(t['tof0']), _ptr(t['status'])
+        for k, rows in (('xi', self.NRXN), ('sf', self.NRXN), ('sr', self.NRXN), ('order', self.NFIX),
+                        ('order_in', self.NDYN), ('dir', nd)):
+            t[k] = t[k][:rows]
+        return o, dirs, t, keep
+
+    def sens_at(self, n, T, p, y, kf, kr, desc=None, fixc=None, inflow=None, status_in=None, directions=None,
+                err_max=1e-9):
+        """pck_sens_at: the adjoint sensitivities at the steady states y
+        [NDYN, n] (kf, kr [NRXN, n]).  directions = (a, c), [ND, NRXN, n] each
+        (or [NRXN, n] for one): d ln kf, d ln kr.  Returns dict(xi, sf, sr
+        [NRXN, n], order [NFIX, n], order_in [NDYN, n], dir [ND, n], err, tof0,
+        status [n]); a condition with err > err_max has status 8 and NaN in
+        everything but xi, tof0, err (err_max <= 0: no guard)."""
+        torch = self.torch
+        c, keep = self.conditions(n, T, p, desc, fixc, None, inflow)
+        y = torch.as_tensor(y, dtype=torch.float64, device='cuda').reshape(self.NDYN, n).contiguous()
+        kf = torch.as_tensor(kf, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        kr = torch.as_tensor(kr, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        si = None
+        if status_in is not None:
+            si = torch.as_tensor(status_in, dtype=torch.int32, device='cuda').reshape(-1).contiguous()
+            if si.numel() != n:
+                raise ValueError('status_in has %d entries for %d conditions' % (si.numel(), n))
+        o, dirs, out, keep2 = self._sens_io(n, directions)
+        L.check(self.lib.pck_sens_at(self.h, C.byref(c), _ptr(kf), _ptr(kr), n, _ptr(y), n, _ptr(si),
+                                     C.byref(dirs) if dirs is not None else None, float(err_max), C.byref(o),
+                                     _stream(torch)))
+        return out
+
+    def sens_adjoint(self, n, T, p, y0, desc=None, fixc=None, inflow=None, directions=None, err_max=1e-9, **kw):
+        """pck_sens_adjoint: one steady solve (kw as for solve; newton=True is
+        required) and sens_at at its states.  Returns what sens_at returns
+        plus nsteps."""
+        torch = self.torch
+        c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)
+        prm = self.params(**kw)
+        o, dirs, out, keep2 = self._sens_io(n, directions)
+        out['nsteps'] = torch.empty(n, dtype=torch.int32, device='cuda')
+        L.check(self.lib.pck_sens_adjoint(self.h, C.byref(c), C.byref(prm), C.byref(dirs) if dirs is not None else None,
+                                          float(err_max), C.byref(o), _ptr(out['nsteps']), _stream(torch)))
+        return out
+
 
 _form_cache = {}
 
