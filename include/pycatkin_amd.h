@@ -405,6 +405,23 @@ int pck_sens_adjoint(const pck_network* net, const pck_conditions* cond, const p
                      const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out, int32_t* nsteps,
                      void* stream);
 
+/* Lanes per condition of the adjoint kernels behind pck_drc_at, pck_drc_adjoint,
+ * pck_sens_at and pck_sens_adjoint: PCK_SENS_LANES_GROUP (default: G = 16, 32 or 64
+ * lanes own one condition, csrc/mk_sens.h), PCK_SENS_LANES_ONE (one lane per
+ * condition, csrc/mk_sens_lane.h: the same formulas, statuses and outputs, every
+ * step serial in its lane; networks of up to PCK_MAX_DYN_LANE dynamic species, else
+ * PCK_E_SIZE from this call), PCK_SENS_LANES_AUTO (one lane up to PCK_MAX_DYN_LANE
+ * species, else the group kernels).  Any other mode is PCK_E_ARG.  The two kinds
+ * agree to rounding, not bitwise (sums over reactions run in another order); the
+ * argument checks of the four entry points are the same in every mode. */
+#define PCK_SENS_LANES_GROUP 0
+#define PCK_SENS_LANES_ONE 1
+#define PCK_SENS_LANES_AUTO 2
+int pck_network_set_sens_lanes(pck_network* net, int mode);
+/* Lanes per condition of the last adjoint launch: 1, 16, 32 or 64; 0 before any.
+ * Diagnostic, as pck_network_group_lanes: which kernel answered. */
+int pck_network_sens_lanes(const pck_network* net, int32_t* lanes);
+
 /* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
  * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program
  * register that holds its energy (eV).  Entry 0 is the reference every energy

@@ -573,7 +573,7 @@ class System:
         return out
 
     def drc_batch(self, tof_terms, T=None, p=None, desc=None, eps=1.0e-3, steady=False, t_end=None, rtol=None,
-                  atol=None, max_steps=200000, y0=None, fix=None, inflow=None, screen='auto', method='fd'):
+                  atol=None, max_steps=200000, y0=None, fix=None, inflow=None, screen='auto', method='fd', adjoint_kernel='group'):
         """Degree of rate control of every reaction (old_system.py:490-515) for a batch.
         steady=True: each of the 2R+1 solves is a steady-state solve with
         solve_batch's rule (STEADY_TRANSIENT unless rtol / atol are given;
@@ -591,6 +591,7 @@ class System:
         did not report a reached root keeps that status (4, ...) and gets NaN
         xi: a transient end has no implicit-function sensitivity; status 7: a
         singular steady Jacobian.  `screen` then applies to the one solve.
+        `adjoint_kernel` ('analytic' only): as in drc_at.
 
         Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0', 'status'
         and 'nsteps'."""
@@ -599,8 +600,11 @@ class System:
         if method == 'analytic' and not steady:
             raise ValueError("method='analytic' needs steady=True: the analytic degree of rate control is "
                              "the sensitivity of a steady state")
+        mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
+        if method == 'analytic':
+            net.set_sens_lanes(mode)
         n = self._n(T, p, *(desc.values() if desc else []))
         for a in (y0, fix, inflow):
             if a is not None and np.ndim(a) == 2:
@@ -632,16 +636,31 @@ class System:
             out['nsteps'] = r['nsteps'].cpu().numpy()
         return out
 
-    def drc_at(self, tof_terms, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None, k=None):
+    @staticmethod
+    def _adjoint_mode(adjoint_kernel):
+        """pck_network_set_sens_lanes' mode of adjoint_kernel = 'group' | 'lane' | 'auto'."""
+        if not isinstance(adjoint_kernel, str) or adjoint_kernel not in _L.SENS_LANES_MODES:
+            raise ValueError("adjoint_kernel must be 'group', 'lane' or 'auto', not %r" % (adjoint_kernel,))
+        return _L.SENS_LANES_MODES[adjoint_kernel]
+
+    def drc_at(self, tof_terms, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None, k=None,
+               adjoint_kernel='group'):
         """Analytic degree of rate control (drc_batch's method='analytic') at
         given steady states Y [n_dynamic, n] in plan.dyn order -- solve_batch's
         'y' -- without a solve (pck_drc_at).  The states are taken as steady.
         status_in ([n], optional): only its 0 rows are computed, the others
         keep their status and get NaN xi.  k = (kf, kr) [active reactions, n]:
         rate constants to use instead of the network's own at (T, p, desc).
+        adjoint_kernel: 'group' (16, 32 or 64 lanes per condition, the
+        default), 'lane' (one lane per condition: networks of at most 8 dynamic
+        species, a larger one raises) or 'auto' ('lane' where the network
+        allows it); the two kernels agree to rounding (DESIGN.md "One-lane
+        adjoint").
         Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0' and 'status'."""
+        mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
+        net.set_sens_lanes(mode)
         Y = np.asarray(Y, float)
         if Y.ndim == 1:
             Y = Y[:, None]
@@ -738,7 +757,7 @@ class System:
         return None if a is None else (a, c)
 
     def sensitivity_at(self, tof_terms, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None, k=None,
-                       directions=None, err_max=1.0e-9, eapp=False):
+                       directions=None, err_max=1.0e-9, eapp=False, adjoint_kernel='group'):
         """First-order sensitivities of the TOF at given steady states Y
         [n_dynamic, n] (plan.dyn order), from the adjoint solve of the analytic
         degree of rate control (pck_sens_at) -- arguments as drc_at.  Returns
@@ -758,11 +777,13 @@ class System:
         A condition whose err = 2^-98 max rate / |TOF| exceeds err_max has
         status 8 and NaN everywhere but 'xi', 'tof0', 'err': double-double no
         longer resolves the per-direction numbers there (err_max <= 0: no
-        guard)."""
+        guard).  adjoint_kernel: as in drc_at."""
+        mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan(tuple(tof_terms), None)
         if eapp:
             self._eapp_check(plan)
         net = self.device(tuple(tof_terms), None)
+        net.set_sens_lanes(mode)
         Y = np.asarray(Y, float)
         if Y.ndim == 1:
             Y = Y[:, None]
@@ -777,18 +798,21 @@ class System:
 
     def sensitivity_batch(self, tof_terms, T=None, p=None, desc=None, steady=True, t_end=None, rtol=None, atol=None,
                           max_steps=200000, y0=None, fix=None, inflow=None, screen='auto', directions=None,
-                          eapp=False, err_max=1.0e-9):
+                          eapp=False, err_max=1.0e-9, adjoint_kernel='group'):
         """One steady solve per condition (drc_batch's rule and options) and
         sensitivity_at at its states, in two launches (pck_sens_adjoint).
         Returns sensitivity_at's dict plus 'nsteps'.  A condition whose solve
-        did not report a reached root keeps that status (4, ...) and gets NaN."""
+        did not report a reached root keeps that status (4, ...) and gets NaN.
+        adjoint_kernel: as in drc_at."""
         if not steady:
             raise ValueError('sensitivity_batch needs steady=True: the adjoint sensitivities are those of a '
                              'steady state')
+        mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan(tuple(tof_terms), None)
         if eapp:
             self._eapp_check(plan)
         net = self.device(tuple(tof_terms), None)
+        net.set_sens_lanes(mode)
         n = self._n(T, p, *(desc.values() if desc else []))
         for a in (y0, fix, inflow):
             if a is not None and np.ndim(a) == 2:
@@ -807,6 +831,171 @@ class System:
                              newton=True, root_dist=ROOT_DIST,
                              screen=(float(screen), SCREEN_MARGIN) if screen else None)
         return self._sens_dict(plan, r, n, T, eapp)
+
+    # -- descriptor sensitivities (DESIGN.md "One-lane adjoint") ----------------------------
+    @staticmethod
+    def _desc_names(plan, names):
+        """The descriptors to differentiate in: `names`, or every descriptor of
+        the plan that is not temperature-keyed."""
+        if names is None:
+            return [k for k in plan.descriptors if not k.startswith('@T:')]
+        names = [names] if isinstance(names, str) else [str(k) for k in names]
+        for k in names:
+            if k.startswith('@T:'):
+                raise ValueError('descriptor %r is a temperature-keyed user energy: a tabulated energy is no '
+                                 'descriptor to differentiate in' % (k,))
+            if k not in plan.descriptors:
+                raise ValueError('unknown descriptor %r (the plan has %s)'
+                                 % (k, ', '.join(x for x in plan.descriptors if not x.startswith('@T:')) or 'none'))
+        return names
+
+    def _dlnk_ddesc(self, net, plan, n, T, p, d, names, h):
+        """{name: (d ln kf / d desc, d ln kr / d desc)} [NRXN, n] on the device:
+        the 5-point central stencil of the network's rate constants in that
+        descriptor at the absolute step h (four launches per descriptor), 0
+        where a rate constant is 0.  The twin of _dlnk_dT."""
+        torch = net.torch
+        dt = torch.as_tensor(d, dtype=torch.float64, device='cuda')
+        zero = torch.zeros((), dtype=torch.float64, device='cuda')
+        out = {}
+        for name in names:
+            q = list(plan.descriptors).index(name)
+            acc = [0.0, 0.0]
+            live = [None, None]
+            for m, w in ((-2.0, 1.0), (-1.0, -8.0), (1.0, 8.0), (2.0, -1.0)):
+                dm = dt.clone()
+                dm[q] += m * h
+                k = net.rate_constants(n, T, p, dm)
+                for s in (0, 1):
+                    acc[s] = acc[s] + w * torch.log(k[s])
+                    live[s] = k[s] > 0.0
+            out[name] = tuple(torch.where(live[s], acc[s] / (12.0 * h), zero) for s in (0, 1))
+        return out
+
+    def dlnk_ddesc_batch(self, names=None, T=None, p=None, desc=None, h=1.0e-3):
+        """{descriptor: (a, c)} with (a, c) = (d ln kf / d desc, d ln kr / d desc),
+        [active reactions, n] device tensors in 1/eV, at fixed T, p and the
+        other descriptors: the directions whose sensitivity is d ln TOF / d
+        desc (descriptor_sensitivity_batch).  5-point central stencil of the
+        rate constants at the absolute step h (eV); 0 where a rate constant is
+        0 (irreversible steps).  names=None: every descriptor of the plan that
+        is not temperature-keyed; an '@T:' key or an unknown name raises
+        ValueError.  The derivative is undefined where an energy clamp of the
+        energy program (max(dGa, 0), the register clamps) switches within 2 h
+        of the point: the stencil then straddles the kink."""
+        plan = self.plan((), None)
+        names = self._desc_names(plan, names)
+        net = self.device((), None)
+        n = self._n(T, p, *(desc or {}).values()) if isinstance(desc, dict) else \
+            (max(self._n(T, p), int(desc.shape[1])) if desc is not None else self._n(T, p))
+        T, p, d, _, _, _ = self._inputs(net, plan, n, T, p, desc, None, None, None)
+        return self._dlnk_ddesc(net, plan, n, T, p, d, names, float(h))
+
+    @staticmethod
+    def _desc_sigma(names, desc_sigma):
+        if desc_sigma is None:
+            return None
+        extra = [k for k in desc_sigma if k not in names]
+        if extra:
+            raise ValueError('desc_sigma has %s, not among the requested descriptors %s' % (extra, names))
+        return {k: float(desc_sigma[k]) for k in names if k in desc_sigma}
+
+    def _desc_sens_dict(self, plan, r, n, names, sigma):
+        h = {k: v.cpu().numpy() for k, v in r.items()}
+        out = {'dlntof_ddesc': {name: h['dir'][m] for m, name in enumerate(names)},
+               'xi': {name: (h['xi'][plan.reactions.index(name)] if name in plan.reactions else np.zeros(n))
+                      for name in plan.all_reactions}}
+        for key in ('tof0', 'status', 'err', 'nsteps'):
+            if key in h:
+                out[key] = h[key]
+        if sigma is not None:
+            # first-order propagation of independent descriptor errors
+            out['std_lntof'] = np.sqrt(sum((out['dlntof_ddesc'][k] * s) ** 2 for k, s in sigma.items()))
+        return out
+
+    def _desc_directions(self, net, plan, n, T, p, d, names, h):
+        torch = net.torch
+        ac = self._dlnk_ddesc(net, plan, n, T, p, d, names, h)
+        return torch.stack([ac[k][0] for k in names]), torch.stack([ac[k][1] for k in names])
+
+    def descriptor_sensitivity_at(self, tof_terms, Y, T=None, p=None, desc=None, fix=None, inflow=None,
+                                  status_in=None, k=None, names=None, desc_sigma=None, err_max=1.0e-9,
+                                  adjoint_kernel='auto', h=1.0e-3):
+        """d ln TOF / d descriptor at given steady states Y [n_dynamic, n]
+        (arguments as sensitivity_at): the (a, c) of dlnk_ddesc_batch stacked as
+        directions of one adjoint solve (pck_sens_at).  Returns
+          'dlntof_ddesc'   {descriptor: [n]} in 1/eV, for `names` (None: every
+                           descriptor that is not temperature-keyed)
+          'xi'             {reaction: [n]}
+          'tof0', 'status', 'err' [n]
+          'std_lntof'      [n] with desc_sigma = {descriptor: sigma in eV}:
+                           sqrt(sum_d (dlntof_ddesc_d sigma_d)^2), the first-order
+                           error bar of ln TOF for independent descriptor errors
+        Guard and statuses as sensitivity_at: NaN gradients where the status
+        is not 0.  The gradients inherit dlnk_ddesc_batch's caveat at energy
+        clamps.  adjoint_kernel: as in drc_at ('auto': one lane per condition
+        where the network allows it)."""
+        mode = self._adjoint_mode(adjoint_kernel)
+        plan = self.plan(tuple(tof_terms), None)
+        names = self._desc_names(plan, names)
+        sigma = self._desc_sigma(names, desc_sigma)
+        if not names:
+            raise ValueError('descriptor sensitivities: the network has no descriptor')
+        net = self.device(tuple(tof_terms), None)
+        net.set_sens_lanes(mode)
+        Y = np.asarray(Y, float)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.shape[0] != net.NDYN:
+            raise ValueError('Y has %d rows for %d dynamic species' % (Y.shape[0], net.NDYN))
+        n = Y.shape[1]
+        T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
+        dirs = self._desc_directions(net, plan, n, T, p, d, names, float(h))
+        kf, kr = net.rate_constants(n, T, p, d) if k is None else k
+        r = net.sens_at(n, T, p, Y, kf, kr, d, fx, inflow, status_in, directions=dirs, err_max=err_max)
+        return self._desc_sens_dict(plan, r, n, names, sigma)
+
+    def descriptor_sensitivity_batch(self, tof_terms, T=None, p=None, desc=None, names=None, desc_sigma=None,
+                                     adjoint_kernel='auto', steady=True, t_end=None, rtol=None, atol=None,
+                                     max_steps=200000, y0=None, fix=None, inflow=None, screen='auto',
+                                     err_max=1.0e-9, h=1.0e-3):
+        """One steady solve per condition (sensitivity_batch's rule and options)
+        and descriptor_sensitivity_at at its states (pck_sens_adjoint): d ln TOF
+        / d E_CO and d ln TOF / d E_O at every node of a volcano grid, and with
+        desc_sigma the error bar they imply.  Returns
+        descriptor_sensitivity_at's dict plus 'nsteps'."""
+        if not steady:
+            raise ValueError('descriptor_sensitivity_batch needs steady=True: the adjoint sensitivities are those '
+                             'of a steady state')
+        mode = self._adjoint_mode(adjoint_kernel)
+        plan = self.plan(tuple(tof_terms), None)
+        names = self._desc_names(plan, names)
+        sigma = self._desc_sigma(names, desc_sigma)
+        if not names:
+            raise ValueError('descriptor sensitivities: the network has no descriptor')
+        net = self.device(tuple(tof_terms), None)
+        net.set_sens_lanes(mode)
+        if desc is not None and not isinstance(desc, dict):
+            n = max(self._n(T, p), int(desc.shape[1]))
+        else:
+            n = self._n(T, p, *(desc.values() if desc else []))
+        for a in (y0, fix, inflow):
+            if a is not None and np.ndim(a) == 2:
+                n = max(n, np.shape(a)[1])
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)
+        dirs = self._desc_directions(net, plan, n, T, p, d, names, float(h))
+        times = self.params['times'] or [0.0, 1.0e4]
+        rtol = STEADY_TRANSIENT[0] if rtol is None else rtol
+        atol = STEADY_TRANSIENT[1] if atol is None else atol
+        if isinstance(screen, str):
+            if screen != 'auto':
+                raise ValueError("screen must be 'auto', None or an rtol")
+            screen = SCREEN_RTOL if net.NDYN <= SCREEN_MAX_LANE_SPECIES else None
+        r = net.sens_adjoint(n, T, p, y0, d, fx, inflow, directions=dirs, err_max=err_max, t0=times[0],
+                             t_end=times[-1] if t_end is None else t_end, rtol=rtol, atol=atol, max_steps=max_steps,
+                             newton=True, root_dist=ROOT_DIST,
+                             screen=(float(screen), SCREEN_MARGIN) if screen else None)
+        return self._desc_sens_dict(plan, r, n, names, sigma)
 
     # -- reference API (one condition) -------------------------------------------------
     def _full(self, plan, ydyn):

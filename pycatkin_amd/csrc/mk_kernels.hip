@@ -47,6 +47,8 @@ struct pck_network {
     mutable std::atomic<bool> grp_ct_on{false};   // ... with the network compiled in (mk_group.h: ct_rhs)
     mutable std::atomic<bool> grp_quad_on{false}; // ... the quad-group kernel (mk_quad.h)
     mutable std::atomic<int> grp_lanes{0};        // lanes per condition of the last lane-group solve
+    int sens_mode = PCK_SENS_LANES_GROUP;         // pck_network_set_sens_lanes
+    mutable std::atomic<int> sens_lanes{0};       // lanes per condition of the last adjoint launch
 };
 
 // FNV-1a 64 over the solver-side structure (network.py: structural_digest)
@@ -259,6 +261,7 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 
 #include "mk_solver.h"
 #include "mk_sens.h"
+#include "mk_sens_lane.h"
 
 // The solver kernels are compiled in translation units of their own in the
 // product build (csrc/mk_inst.h, csrc/tu_*.hip): here they are only declared.
@@ -659,6 +662,22 @@ extern "C" int pck_network_dims(const pck_network* net, int32_t* dims) {
 extern "C" int pck_network_group_lanes(const pck_network* net, int32_t* lanes) {
     if (!net || !lanes) return fail(PCK_E_ARG, "null argument%s", "");
     *lanes = net->grp_lanes.load(std::memory_order_relaxed);
+    return PCK_OK;
+}
+
+extern "C" int pck_network_set_sens_lanes(pck_network* net, int mode) {
+    if (!net) return fail(PCK_E_ARG, "null network%s", "");
+    if (mode < PCK_SENS_LANES_GROUP || mode > PCK_SENS_LANES_AUTO)
+        return fail(PCK_E_ARG, "unknown adjoint lane mode%s %lld", "", mode);
+    if (mode == PCK_SENS_LANES_ONE && net->nv.NDYN > PCK_MAX_DYN_LANE)
+        return fail(PCK_E_SIZE, "one-lane adjoint: at most %s%lld dynamic species", "", PCK_MAX_DYN_LANE);
+    net->sens_mode = mode;
+    return PCK_OK;
+}
+
+extern "C" int pck_network_sens_lanes(const pck_network* net, int32_t* lanes) {
+    if (!net || !lanes) return fail(PCK_E_ARG, "null argument%s", "");
+    *lanes = net->sens_lanes.load(std::memory_order_relaxed);
     return PCK_OK;
 }
 
@@ -1487,6 +1506,18 @@ extern "C" int pck_drc(const pck_network* net, const pck_conditions* cond, const
 // ----------------------------------------------------------------------------
 // analytic DRC (csrc/mk_sens.h)
 // ----------------------------------------------------------------------------
+// one lane per condition (csrc/mk_sens_lane.h) by the network's mode (pck_network_set_sens_lanes)
+static inline bool sens_one_lane(const pck_network* net) {
+    return net->sens_mode != PCK_SENS_LANES_GROUP && net->nv.NDYN <= PCK_MAX_DYN_LANE;
+}
+// dynamic LDS of a one-lane launch, sized by NS: 24 KiB at NS 4, 80 KiB at 8.
+// Above the 64 KiB a kernel may ask for by default its limit is raised (a CU has 160 KiB).
+static int sens_lane_lds(const void* kernel, int NS, size_t* shm) {
+    *shm = sens_lane_lds_bytes(NS);
+    if (*shm > 64 * 1024) HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*shm));
+    return PCK_OK;
+}
+
 static int launch_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
                          int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in, double* xi,
                          int64_t ld_xi, double* tof0, int32_t* status, hipStream_t s) {
@@ -1497,6 +1528,18 @@ static int launch_drc_at(const pck_network* net, const pck_conditions* cond, con
     if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "analytic DRC: 1..%s%lld reactions", "", PCK_MAX_RXN);
     if (!net->grp_ok) return fail(PCK_E_SIZE, "analytic DRC (record tables): %s", net->grp_why);
     if (net->nv.NTOF < 1) return fail(PCK_E_ARG, "analytic DRC: the network has no TOF terms%s", "");
+    if (sens_one_lane(net)) {                      // csrc/mk_sens_lane.h
+        const int64_t nbl = (n + 63) / 64;
+        if (nbl > 0x7fffffffLL) return fail(PCK_E_SIZE, "analytic DRC: more than 2^31 - 1 workgroups%s", "");
+        size_t shml = 0;
+        const int rc = sens_lane_lds((const void*)k_lane_drc_adjoint, NS, &shml);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_lane_drc_adjoint, dim3((unsigned)nbl), dim3(64), shml, s, net->nv, net->gv, cview(cond), kf,
+                           kr, ld_k, y, ld_y, status_in, xi, ld_xi, tof0, status);
+        HIPCHK(hipGetLastError());
+        net->sens_lanes.store(1, std::memory_order_relaxed);
+        return PCK_OK;
+    }
     const int G = grp_g(NS), per = 64 / G;
     const int64_t nb = (n + per - 1) / per;
     if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "analytic DRC: more than 2^31 - 1 workgroups%s", "");
@@ -1508,6 +1551,7 @@ static int launch_drc_at(const pck_network* net, const pck_conditions* cond, con
     else CALL(64);
 #undef CALL
     HIPCHK(hipGetLastError());
+    net->sens_lanes.store(G, std::memory_order_relaxed);
     return PCK_OK;
 }
 
@@ -1540,6 +1584,18 @@ static int launch_sens_at(const pck_network* net, const pck_conditions* cond, co
         ex.a = dirs->a; ex.c = dirs->c; ex.ld_ac = dirs->ld; ex.s_ac = dirs->stride; ex.nd = (int)dirs->nd;
         ex.dir = out->dir; ex.ld_dir = out->ld_dir;
     }
+    if (sens_one_lane(net)) {                      // csrc/mk_sens_lane.h
+        const int64_t nbl = (n + 63) / 64;
+        if (nbl > 0x7fffffffLL) return fail(PCK_E_SIZE, "adjoint sensitivities: more than 2^31 - 1 workgroups%s", "");
+        size_t shml = 0;
+        const int rc = sens_lane_lds((const void*)k_lane_sens_adjoint, NS, &shml);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_lane_sens_adjoint, dim3((unsigned)nbl), dim3(64), shml, s, net->nv, net->gv, cview(cond), kf,
+                           kr, ld_k, y, ld_y, status_in, out->xi, out->ld_xi, out->tof0, out->status, ex);
+        HIPCHK(hipGetLastError());
+        net->sens_lanes.store(1, std::memory_order_relaxed);
+        return PCK_OK;
+    }
     const int G = grp_g(NS), per = 64 / G;
     const int64_t nb = (n + per - 1) / per;
     if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "adjoint sensitivities: more than 2^31 - 1 workgroups%s", "");
@@ -1551,6 +1607,7 @@ static int launch_sens_at(const pck_network* net, const pck_conditions* cond, co
     else CALL(64);
 #undef CALL
     HIPCHK(hipGetLastError());
+    net->sens_lanes.store(G, std::memory_order_relaxed);
     return PCK_OK;
 }
 

@@ -73,6 +73,21 @@ class DeviceNetwork:
         L.check(self.lib.pck_network_group_lanes(self.h, C.byref(g)))
         return int(g.value)
 
+    def set_sens_lanes(self, mode):
+        """Lanes per condition of the adjoint kernels (drc_at, drc_adjoint,
+        sens_at, sens_adjoint): 0 = the 16- / 32- / 64-lane group kernels (the
+        default), 1 = one lane per condition (networks of up to 8 dynamic
+        species; a larger one raises), 2 = one lane where the network allows
+        it, else the group kernels (pck_network_set_sens_lanes)."""
+        L.check(self.lib.pck_network_set_sens_lanes(self.h, int(mode)))
+
+    def sens_lanes(self):
+        """Lanes per condition of the last adjoint launch: 1, 16, 32 or 64; 0
+        before any."""
+        g = C.c_int32(0)
+        L.check(self.lib.pck_network_sens_lanes(self.h, C.byref(g)))
+        return int(g.value)
+
     def set_plan_mode(self, mode):
         """A/B switch: 0 / False = auto, 1 / True = runtime plan (never the
         compiled-in one), 2 = lane-group solver."""

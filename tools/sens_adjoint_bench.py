@@ -4,7 +4,11 @@ k_sens_adjoint) against the analytic degree of rate control they extend
 sensitivity_batch(eapp=True) path against the steady solve it starts with.
 
 Workloads as tools/drc_adjoint_bench.py: dmtm (64 x 64 grid), syn24 (4 096
-conditions), volcano (1024 x 1024 grid).  Per workload, on the current stream:
+conditions), volcano (1024 x 1024 grid); cstr (the Pd111 CSTR, a sweep of 10 000
+temperatures 423 .. 623 K; its Eapp is refused -- the row scale depends on T -- so
+its direction is the fixed a = c = 1).  --adjoint-kernel group | lane picks the
+adjoint kernels (csrc/mk_sens.h / csrc/mk_sens_lane.h; lane: networks of at
+most 8 dynamic species).  Per workload, on the current stream:
   solve       pck_solve alone (System.sensitivity_batch's settings)
   drc_at      pck_drc_at at the solve's states: k_drc_adjoint alone
   sens_at     pck_sens_at at the same states, every output, one direction
@@ -17,7 +21,8 @@ conditions), volcano (1024 x 1024 grid).  Per workload, on the current stream:
 HIP events around `reps` back-to-back calls, the median of `--rounds` rounds
 with the spread.  Prints one JSON line per workload.  Needs the GPU.
 
-    python tools/sens_adjoint_bench.py [--workloads dmtm,syn24,volcano] [--rounds 5]
+    python tools/sens_adjoint_bench.py [--workloads dmtm,syn24,volcano,cstr] [--rounds 5]
+                                       [--adjoint-kernel group|lane]
 """
 import argparse
 import ctypes as C
@@ -38,6 +43,7 @@ def run(name, sim, terms, kw, n, a, torch):
     from pycatkin_amd.classes.system import (ROOT_DIST, SCREEN_MARGIN, SCREEN_MAX_LANE_SPECIES, SCREEN_RTOL,
                                              STEADY_TRANSIENT)
     plan, net = sim.plan(terms), sim.device(terms)
+    net.set_sens_lanes(L.SENS_LANES_MODES[a.adjoint_kernel])
     T, p, d, fx, y0, inflow = sim._inputs(net, plan, n, kw['T'], kw.get('p'), kw.get('desc'), None, None, None)
     times = sim.params['times'] or [0.0, 1.0e4]
     screen = (SCREEN_RTOL, SCREEN_MARGIN) if net.NDYN <= SCREEN_MAX_LANE_SPECIES else None
@@ -56,7 +62,10 @@ def run(name, sim, terms, kw, n, a, torch):
         state['t'] = net.drc_at(n, T, p, state['s']['y'], kf, kr, d, fx, inflow, state['s']['status'])
 
     def dlnk():
-        state['k'] = sim._dlnk_dT(net, n, T, p, d)
+        if name == 'cstr':
+            state['k'] = (torch.ones_like(kf), torch.ones_like(kr))
+        else:
+            state['k'] = sim._dlnk_dT(net, n, T, p, d)
 
     def sens_at():
         state['e'] = net.sens_at(n, T, p, state['s']['y'], kf, kr, d, fx, inflow, state['s']['status'],
@@ -95,7 +104,7 @@ def run(name, sim, terms, kw, n, a, torch):
     for _ in range(a.rounds):
         for k, fn in todo:
             ms[k].append(timed(fn, a.reps))
-    res = dict(workload=name, conditions=n, species=net.NDYN, reactions=net.NRXN, fixed=net.NFIX)
+    res = dict(workload=name, adjoint_kernel=a.adjoint_kernel, lanes_per_condition=net.sens_lanes(), conditions=n, species=net.NDYN, reactions=net.NRXN, fixed=net.NFIX)
     for k, v in ms.items():
         res[k + '_ms'] = round(float(np.median(v)), 4)
         res[k + '_ms_min_max'] = [round(float(min(v)), 4), round(float(max(v)), 4)]
@@ -110,6 +119,11 @@ def run(name, sim, terms, kw, n, a, torch):
     print(json.dumps(res), flush=True)
 
 
+def cstr(P, n):
+    sim = P.read_from_input_file(os.path.join(ROOT, 'tests', 'golden', 'inputs', 'COOxReactor', 'input_Pd111.json'))
+    return sim, ('CO_ox',), dict(T=np.linspace(423.0, 623.0, n)), n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workloads', default='dmtm,syn24,volcano')
@@ -118,13 +132,15 @@ def main():
     ap.add_argument('--syn24-n', type=int, default=4096)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--cstr-n', type=int, default=10000)
+    ap.add_argument('--adjoint-kernel', choices=('group', 'lane'), default='group')
     a = ap.parse_args()
     import torch
     import pycatkin_amd as P
     import drc_adjoint_bench as B
-    size = dict(dmtm=a.dmtm_grid, volcano=a.volcano_grid, syn24=a.syn24_n)
+    size = dict(dmtm=a.dmtm_grid, volcano=a.volcano_grid, syn24=a.syn24_n, cstr=a.cstr_n)
     for name in a.workloads.split(','):
-        sim, terms, kw, n = dict(dmtm=B.dmtm, volcano=B.volcano, syn24=B.syn24)[name](P, size[name])
+        sim, terms, kw, n = dict(dmtm=B.dmtm, volcano=B.volcano, syn24=B.syn24, cstr=cstr)[name](P, size[name])
         run(name, sim, terms, kw, n, a, torch)
 
 
