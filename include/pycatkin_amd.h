@@ -33,6 +33,8 @@
  *   pck_drc_adjoint        analytic: one steady solve + one adjoint solve instead of 2R+1 solves)
  *   pck_sens_at         <- (none: the reference has no reaction orders, apparent activation
  *   pck_sens_adjoint       energy or per-direction sensitivities; the same adjoint solve gives them)
+ *   pck_drc_multi_at    <- (none: selectivity and coverage control, the rate-control matrix:
+ *   pck_drc_multi_adjoint  K objectives passed per call, one factorisation, K adjoint solves)
  *   pck_energy_span     <- Energy.construct_energy_landscape  pycatkin/classes/energy.py:39
  *                          Energy.evaluate_energy_span_model  energy.py:238
  *   pck_ensemble_noise  <- Uncertainty.get_correlated_state_noises pycatkin/classes/uncertainty.py:35
@@ -421,6 +423,62 @@ int pck_network_set_sens_lanes(pck_network* net, int mode);
 /* Lanes per condition of the last adjoint launch: 1, 16, 32 or 64; 0 before any.
  * Diagnostic, as pck_network_group_lanes: which kernel answered. */
 int pck_network_sens_lanes(const pck_network* net, int32_t* lanes);
+
+/* Multi-objective analytic degree of rate control: K objectives that are data of the
+ * call, not of the plan (a network without TOF terms is accepted),
+ *   J_m = sum_j wr[m][j] net_j + sum_i wy[m][i] y_i,
+ * net_j the net rate of active reaction j (plan order), y_i the state variable of
+ * dynamic species i as given (not its concentration cf_i y_i): a sum of net rates
+ * (a TOF; num and den of a selectivity), a coverage or a CSTR's outlet concentration
+ * (one entry of wy), or any mix.  Device pointers, per network, not per condition;
+ * either may be NULL (all zero), not both. */
+typedef struct {
+    int K;                            /* number of objectives, >= 1 */
+    const double* wr;                 /* [K][NRXN] */
+    const double* wy;                 /* [K][NDYN] */
+} pck_multi_obj;
+
+/* Device pointers; [rows][ld] with ld >= n.  val and xi are required. */
+typedef struct {
+    double* val; int64_t ld_val;      /* [K][ld_val]  J_m at the given states (every condition) */
+    double* xi; int64_t ld_xi;        /* [K * NRXN][ld_xi]  row m * NRXN + j: d ln J_m / d ln k_j at fixed K_j */
+    int32_t* status;                  /* [n]  PCK_ST_* of the condition (optional) */
+    int32_t* ostatus; int64_t ld_os;  /* [K][ld_os]  PCK_ST_* of each objective (optional) */
+} pck_multi_out;
+
+/* The degree of rate control of K objectives at given steady states y ([NS][ld_y]),
+ * kf / kr as pck_rate_constants gives them (the reference has none of this: its
+ * degree_of_rate_control knows one TOF; replaces nothing in the reference).
+ * pck_drc_at's assembly and equilibration, one LU factorisation whose multipliers are
+ * kept, and per objective one adjoint solve on the stored factors,
+ *   A^T lambda_m = dJ_m/dy,   xi[m][j] = net_j (wr[m][j] - sum_i lambda_mi w_i S_ij) / J_m
+ * (w_i the row scale, 0 on a replaced row), double-double throughout (csrc/mk_sens_multi.h).
+ * xi_num - xi_den is the control of the selectivity J_num / J_den; a coverage
+ * objective gives d ln theta_i / d ln k_j.  Only val and xi: the per-direction
+ * split, reaction orders and user directions of pck_sens_at are not offered per
+ * objective, since rf_j s_mj / J_m of a coverage objective is not safe in
+ * double-double and no guard is known (DESIGN.md "Multi-objective DRC").
+ * status_in (optional) gates the conditions as in pck_drc_at.  status:
+ * PCK_ST_SENS_SINGULAR for a zero pivot or a non-finite factor; such a condition and a
+ * gated one get NaN in every xi, and that status in every ostatus.  ostatus[m]:
+ * PCK_ST_NONFINITE for a zero or non-finite J_m (or an adjoint solve that overflows):
+ * NaN xi[m][:] for that objective alone.  val is written for every condition.
+ * Always the 16- / 32- / 64-lane group kernels, whatever pck_network_set_sens_lanes
+ * says; pck_network_sens_lanes reports G afterwards.  Sizes as pck_drc_at (PCK_E_SIZE);
+ * PCK_E_ARG: K < 1, NULL obj / out / val / xi, wr and wy both NULL, a leading
+ * dimension below n. */
+int pck_drc_multi_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                     int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+                     const pck_multi_obj* obj, const pck_multi_out* out, void* stream);
+
+/* One steady solve (pck_solve with prm->newton = 1, as pck_drc_adjoint) and then
+ * pck_drc_multi_at at its states, with the solve's own rate constants (replaces
+ * nothing in the reference).  nsteps (optional): the solve's steps.  A condition
+ * whose solve did not report a reached root keeps that status and gets NaN xi (val:
+ * the objectives at the state the solve reports).  PCK_E_ARG: prm->newton == 0, a
+ * trajectory request, and what pck_drc_multi_at refuses. */
+int pck_drc_multi_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                          const pck_multi_obj* obj, const pck_multi_out* out, int32_t* nsteps, void* stream);
 
 /* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
  * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program

@@ -18,7 +18,7 @@ EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_netw
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
             'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
             'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint', 'pck_sens_at', 'pck_sens_adjoint',
-            'pck_network_set_sens_lanes', 'pck_network_sens_lanes')
+            'pck_network_set_sens_lanes', 'pck_network_sens_lanes', 'pck_drc_multi_at', 'pck_drc_multi_adjoint')
 
 ABI_VERSION = 10
 
@@ -94,6 +94,15 @@ class SensDirs(C.Structure):
     _fields_ = [('nd', C.c_int64), ('a', C.c_void_p), ('c', C.c_void_p), ('ld', C.c_int64), ('stride', C.c_int64)]
 
 
+class MultiObj(C.Structure):
+    _fields_ = [('K', C.c_int), ('wr', C.c_void_p), ('wy', C.c_void_p)]
+
+
+class MultiOut(C.Structure):
+    _fields_ = [('val', C.c_void_p), ('ld_val', C.c_int64), ('xi', C.c_void_p), ('ld_xi', C.c_int64),
+                ('status', C.c_void_p), ('ostatus', C.c_void_p), ('ld_os', C.c_int64)]
+
+
 _lib = None
 
 
@@ -136,6 +145,10 @@ def load():
                                 C.POINTER(SensOut), vp]
     lib.pck_sens_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(SensDirs), C.c_double,
                                      C.POINTER(SensOut), vp, vp]
+    lib.pck_drc_multi_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, C.POINTER(MultiObj),
+                                     C.POINTER(MultiOut), vp]
+    lib.pck_drc_multi_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(MultiObj),
+                                          C.POINTER(MultiOut), vp, vp]
     lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
     lib.pck_ensemble_noise.argtypes = [C.c_uint64, C.c_uint64, i64, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, vp]
     lib.pck_ensemble_stats.argtypes = [vp, i64, i64, vp, C.c_uint32, i64, i64, i64, C.POINTER(EnsStats), vp]

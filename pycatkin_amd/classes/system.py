@@ -671,6 +671,184 @@ class System:
         kf, kr = net.rate_constants(n, T, p, d) if k is None else k
         return self._drc_dict(plan, net.drc_at(n, T, p, Y, kf, kr, d, fx, inflow, status_in), n)
 
+    # -- multi-objective DRC (DESIGN.md "Multi-objective DRC") ----------------------------
+    @staticmethod
+    def _objectives(plan, objectives):
+        """(labels, wr [K, active reactions], wy [K, dynamic species]) of a list
+        of objectives: a str names a dynamic species (its coverage / state
+        variable), a tuple or list of reaction names is the sum of their net
+        rates (a name given twice counts twice, as in tof_terms), a dict
+        {'rates': {name: w}, 'species': {name: w}} any weighted mix.  Host work
+        only; ValueError names the offender."""
+        if isinstance(objectives, (str, dict)):
+            objectives = [objectives]
+        objectives = list(objectives)
+        if not objectives:
+            raise ValueError('no objectives')
+        K = len(objectives)
+        wr, wy, labels = np.zeros((K, len(plan.reactions))), np.zeros((K, len(plan.dyn))), []
+
+        def rate(m, name, w):
+            if name not in plan.reactions:
+                what = 'not an active reaction' if name in plan.all_reactions else 'an unknown reaction'
+                raise ValueError('objective %d: %r is %s' % (m, name, what))
+            wr[m, plan.reactions.index(name)] += float(w)
+
+        def species(m, name, w):
+            if name in plan.fix:
+                raise ValueError('objective %d: %r is a fixed species; only a dynamic species has a sensitivity' % (m, name))
+            if name not in plan.dyn:
+                raise ValueError('objective %d: %r is an unknown species' % (m, name))
+            wy[m, plan.dyn.index(name)] += float(w)
+
+        for m, ob in enumerate(objectives):
+            if isinstance(ob, str):
+                species(m, ob, 1.0)
+                labels.append(ob)
+            elif isinstance(ob, (tuple, list)):
+                for name in ob:
+                    if not isinstance(name, str):
+                        raise ValueError('objective %d: %r is not a reaction name' % (m, name))
+                    rate(m, name, 1.0)
+                labels.append('+'.join(ob))
+            elif isinstance(ob, dict):
+                extra = set(ob) - {'rates', 'species', 'label'}
+                if extra:
+                    raise ValueError("objective %d: unknown keys %s (expected 'rates', 'species', 'label')"
+                                     % (m, sorted(extra)))
+                for name, w in (ob.get('rates') or {}).items():
+                    rate(m, name, w)
+                for name, w in (ob.get('species') or {}).items():
+                    species(m, name, w)
+                labels.append(str(ob['label']) if 'label' in ob else ' + '.join(
+                    ['%g %s' % (w, nm) for nm, w in (ob.get('rates') or {}).items()] +
+                    ['%g [%s]' % (w, nm) for nm, w in (ob.get('species') or {}).items()]))
+            else:
+                raise ValueError('objective %d: %r is neither a species name, a list of reaction names nor a dict'
+                                 % (m, ob))
+            if not (wr[m].any() or wy[m].any()):
+                raise ValueError('objective %d (%r) is empty: every weight is zero' % (m, ob))
+        return labels, wr, wy
+
+    def _multi_dict(self, plan, labels, r, n):
+        xi = r['xi'].cpu().numpy()
+        K = xi.shape[0]
+        full = np.zeros((K, len(plan.all_reactions), n))
+        for j, name in enumerate(plan.all_reactions):
+            if name in plan.reactions:
+                full[:, j] = xi[:, plan.reactions.index(name)]
+        out = dict(labels=list(labels), reactions=list(plan.all_reactions), val=r['val'].cpu().numpy(), xi=full,
+                   status=r['status'].cpu().numpy(), ostatus=r['ostatus'].cpu().numpy())
+        if 'nsteps' in r:
+            out['nsteps'] = r['nsteps'].cpu().numpy()
+        return out
+
+    def drc_objectives_at(self, objectives, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None,
+                          k=None):
+        """The analytic degree of rate control of several objectives at given
+        steady states Y [n_dynamic, n] (plan.dyn order), from one factorisation
+        of the steady Jacobian and one adjoint solve per objective
+        (pck_drc_multi_at; DESIGN.md "Multi-objective DRC").  An objective is a
+        str (a dynamic species: its coverage, or a CSTR's outlet concentration),
+        a tuple / list of reaction names (the sum of their net rates, as
+        tof_terms) or a dict {'rates': {name: w}, 'species': {name: w}}; an
+        unknown name, a fixed species or an empty objective raises ValueError.
+        The objectives are data of the call: the plan without TOF terms serves
+        all of them, and changing them never rebuilds a network.  T, p, desc,
+        fix, inflow, status_in and k as in drc_at.
+        Returns dict(labels [K], reactions [R] (every reaction; ghost reactions
+        get 0), val [K, n] (the objectives' values), xi [K, R, n]
+        (d ln J_m / d ln k_j at fixed K_j), status [n], ostatus [K, n] (3: a
+        zero or non-finite objective, NaN xi for it alone))."""
+        plan = self.plan((), None)
+        labels, wr, wy = self._objectives(plan, objectives)
+        net = self.device((), None)
+        Y = np.asarray(Y, float)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.shape[0] != net.NDYN:
+            raise ValueError('Y has %d rows for %d dynamic species' % (Y.shape[0], net.NDYN))
+        n = Y.shape[1]
+        T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
+        kf, kr = net.rate_constants(n, T, p, d) if k is None else k
+        r = net.drc_multi_at(n, T, p, Y, kf, kr, wr, wy, d, fx, inflow, status_in)
+        return self._multi_dict(plan, labels, r, n)
+
+    def drc_objectives_batch(self, objectives, T=None, p=None, desc=None, t_end=None, rtol=None, atol=None,
+                             max_steps=200000, y0=None, fix=None, inflow=None, screen='auto'):
+        """drc_objectives_at at the steady states of one steady solve per
+        condition (pck_drc_multi_adjoint): the arguments of
+        drc_batch(steady=True, method='analytic').  A condition whose solve did
+        not report a reached root keeps that status and gets NaN xi.  Returns
+        what drc_objectives_at returns plus 'nsteps'."""
+        plan = self.plan((), None)
+        labels, wr, wy = self._objectives(plan, objectives)
+        net = self.device((), None)
+        n = self._n(T, p, *(desc.values() if desc else []))
+        for a in (y0, fix, inflow):
+            if a is not None and np.ndim(a) == 2:
+                n = max(n, np.shape(a)[1])
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)
+        times = self.params['times'] or [0.0, 1.0e4]
+        rtol = STEADY_TRANSIENT[0] if rtol is None else rtol
+        atol = STEADY_TRANSIENT[1] if atol is None else atol
+        if isinstance(screen, str):
+            if screen != 'auto':
+                raise ValueError("screen must be 'auto', None or an rtol")
+            screen = SCREEN_RTOL if net.NDYN <= SCREEN_MAX_LANE_SPECIES else None
+        r = net.drc_multi_adjoint(n, T, p, y0, wr, wy, d, fx, inflow, t0=times[0],
+                                  t_end=times[-1] if t_end is None else t_end, rtol=rtol, atol=atol,
+                                  max_steps=max_steps, newton=True, root_dist=ROOT_DIST,
+                                  screen=(float(screen), SCREEN_MARGIN) if screen else None)
+        return self._multi_dict(plan, labels, r, n)
+
+    def _objectives_run(self, objectives, Y, k, status_in, kw):
+        if Y is not None:
+            return self.drc_objectives_at(objectives, Y, k=k, status_in=status_in, **kw)
+        if k is not None or status_in is not None:
+            raise ValueError('k and status_in go with given states Y')
+        return self.drc_objectives_batch(objectives, **kw)
+
+    def selectivity_control_batch(self, num_terms, den_terms, Y=None, k=None, status_in=None, **kw):
+        """Degree of selectivity control d ln (r_num / r_den) / d ln k_j =
+        xi_num - xi_den, with r_num and r_den sums of net rates (reaction names
+        as tof_terms): the two objectives of one launch, so one factorisation.
+        kw as for drc_objectives_batch; with Y (and optionally k, status_in),
+        at those states as drc_objectives_at.
+        Returns dict(reactions [R], dsc [R, n], selectivity [n], status [n] (the
+        condition's, or 3 where either rate is zero or not finite), xi_num,
+        xi_den [R, n], val_num, val_den [n])."""
+        r = self._objectives_run([tuple(num_terms), tuple(den_terms)], Y, k, status_in, kw)
+        st = np.where(r['status'] != 0, r['status'], r['ostatus'].max(axis=0))
+        out = dict(reactions=r['reactions'], dsc=r['xi'][0] - r['xi'][1], selectivity=r['val'][0] / r['val'][1],
+                   status=st, xi_num=r['xi'][0], xi_den=r['xi'][1], val_num=r['val'][0], val_den=r['val'][1])
+        if 'nsteps' in r:
+            out['nsteps'] = r['nsteps']
+        return out
+
+    def coverage_control_batch(self, species=None, Y=None, k=None, status_in=None, **kw):
+        """Degree of coverage control d ln y_i / d ln k_j of the dynamic species
+        `species` (None: every dynamic species, plan.dyn order) -- for a CSTR's
+        gas species the control of its outlet concentration: len(species)
+        objectives of one launch.  kw, Y, k, status_in as in
+        selectivity_control_batch.
+        Returns dict(species, reactions [R], dcc [len(species), R, n], coverage
+        [len(species), n], status [n], ostatus [len(species), n] (3: a species
+        at exactly 0, NaN dcc for it alone))."""
+        if species is None:
+            species = list(self.plan((), None).dyn)
+        elif isinstance(species, str):
+            species = [species]
+        for s in species:
+            if not isinstance(s, str):
+                raise ValueError('%r is not a species name' % (s,))
+        r = self._objectives_run(list(species), Y, k, status_in, kw)
+        out = dict(species=list(species), reactions=r['reactions'], dcc=r['xi'], coverage=r['val'],
+                   status=r['status'], ostatus=r['ostatus'])
+        if 'nsteps' in r:
+            out['nsteps'] = r['nsteps']
+        return out
+
     # -- adjoint sensitivities (DESIGN.md "Adjoint sensitivities") ------------------------
     def _dlnk_dT(self, net, n, T, p, d):
         """(d ln kf / dT, d ln kr / dT) [NRXN, n] on the device: the 5-point

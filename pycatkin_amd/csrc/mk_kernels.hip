@@ -262,6 +262,7 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 #include "mk_solver.h"
 #include "mk_sens.h"
 #include "mk_sens_lane.h"
+#include "mk_sens_multi.h"
 
 // The solver kernels are compiled in translation units of their own in the
 // product build (csrc/mk_inst.h, csrc/tu_*.hip): here they are only declared.
@@ -273,6 +274,9 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 namespace pck {
 #define PCK_X(GG) PCK_DO_SENS(extern, GG)
 PCK_INST_SENS(PCK_X)
+#undef PCK_X
+#define PCK_X(GG) PCK_DO_MULTI(extern, GG)
+PCK_INST_MULTI(PCK_X)
 #undef PCK_X
 #define PCK_X(N) PCK_DO_LANE_RT(extern, N)
 PCK_INST_LANE_RT(PCK_X)
@@ -1706,4 +1710,103 @@ extern "C" int pck_drc_adjoint(const pck_network* net, const pck_conditions* con
     const double* kf = kscr.as<double>();
     const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
     return launch_drc_at(net, cond, kf, kr, n, y, n, st, xi, ld_xi, tof0, status, s);
+}
+
+// ----------------------------------------------------------------------------
+// multi-objective analytic DRC (csrc/mk_sens_multi.h)
+// ----------------------------------------------------------------------------
+static int check_multi(const pck_network* net, int64_t n, const pck_multi_obj* obj, const pck_multi_out* out) {
+    if (!obj || !out) return fail(PCK_E_ARG, "multi-objective DRC: no objectives or no outputs%s", "");
+    if (obj->K < 1) return fail(PCK_E_ARG, "multi-objective DRC: K < 1%s", "");
+    if (!obj->wr && !obj->wy) return fail(PCK_E_ARG, "multi-objective DRC: wr and wy are both NULL%s", "");
+    if (n == 0) return PCK_OK;
+    if (!out->val || !out->xi) return fail(PCK_E_ARG, "multi-objective DRC: val and xi are required%s", "");
+    if (out->ld_val < n || out->ld_xi < n || (out->ostatus && out->ld_os < n))
+        return fail(PCK_E_ARG, "multi-objective DRC: a leading dimension of pck_multi_out is below n%s", "");
+    const int NS = net->nv.NDYN;
+    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "multi-objective DRC: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
+    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "multi-objective DRC: 1..%s%lld reactions", "", PCK_MAX_RXN);
+    if (!net->grp_ok) return fail(PCK_E_SIZE, "multi-objective DRC (record tables): %s", net->grp_why);
+    return PCK_OK;
+}
+
+// always the group kernels, whatever pck_network_set_sens_lanes says; the checks of check_multi are done
+static int launch_multi_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                           int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+                           const pck_multi_obj* obj, const pck_multi_out* out, hipStream_t s) {
+    const int64_t n = cond->n;
+    if (n == 0) return PCK_OK;
+    const int G = grp_g(net->nv.NDYN), per = 64 / G;
+    const int64_t nb = (n + per - 1) / per;
+    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "multi-objective DRC: more than 2^31 - 1 workgroups%s", "");
+    const dim3 g((unsigned)nb);
+    const size_t shm = multi_lds_bytes(G);         // 17 / 33 / 65 KiB
+    const MultiObj ob{obj->K, obj->wr, obj->wy};
+    const MultiOut mo{out->val, out->ld_val, out->xi, out->ld_xi, out->status, out->ostatus, out->ld_os};
+    // above the 64 KiB a kernel may ask for by default its limit is raised (a CU has 160 KiB)
+#define CALL(GG)                                                                                                     \
+    do {                                                                                                             \
+        if (shm > 64 * 1024)                                                                                         \
+            HIPCHK(hipFuncSetAttribute((const void*)k_multi_adjoint<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                       (int)shm));                                                                   \
+        hipLaunchKernelGGL((k_multi_adjoint<GG>), g, dim3(64), shm, s, net->nv, net->gv, cview(cond), kf, kr, ld_k, y, \
+                           ld_y, status_in, ob, mo);                                                                 \
+    } while (0)
+    if (G == 16) CALL(16);
+    else if (G == 32) CALL(32);
+    else CALL(64);
+#undef CALL
+    HIPCHK(hipGetLastError());
+    net->sens_lanes.store(G, std::memory_order_relaxed);
+    return PCK_OK;
+}
+
+// d ln J_m / d ln k_j at given steady states for K objectives J_m that are data of
+// the call: one factorisation, K adjoint solves (the reference has none of this).
+extern "C" int pck_drc_multi_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                                int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
+                                const pck_multi_obj* obj, const pck_multi_out* out, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    if (cond->n > 0 && (!kf || !kr || ld_k < cond->n)) return fail(PCK_E_ARG, "bad kf / kr%s", "");
+    if (cond->n > 0 && (!y || ld_y < cond->n)) return fail(PCK_E_ARG, "bad states y%s", "");
+    rc = check_multi(net, cond->n, obj, out);
+    if (rc) return rc;
+    return launch_multi_at(net, cond, kf, kr, ld_k, y, ld_y, status_in, obj, out, (hipStream_t)stream);
+}
+
+// One steady solve, then pck_drc_multi_at at its states (pck_drc_adjoint's shape).
+extern "C" int pck_drc_multi_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                                     const pck_multi_obj* obj, const pck_multi_out* out, int32_t* nsteps,
+                                     void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    rc = check_params(prm);
+    if (rc) return rc;
+    if (!prm->newton)
+        return fail(PCK_E_ARG, "pck_drc_multi_adjoint needs newton = 1: a transient end has no implicit-function sensitivity%s", "");
+    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "pck_drc_multi_adjoint takes no trajectory request (t_out)%s", "");
+    const int64_t n = cond->n;
+    rc = check_multi(net, n, obj, out);
+    if (rc) return rc;
+    if (n == 0) return PCK_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    const int NS = net->nv.NDYN, R = net->nv.NRXN;
+    StreamScratch yscr;                            // the solve's states and statuses
+    rc = salloc(yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    if (rc) return rc;
+    double* y = yscr.as<double>();
+    int32_t* st = (int32_t*)(y + (int64_t)NS * n);
+    pck_solve_params p = *prm;
+    p.want_activity = 0;
+    SolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = y; a.ld_y = n; a.tof = nullptr; a.status = st; a.nsteps = nsteps;
+    a.G = 1;
+    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
+    rc = launch_solve(net, cond, &p, a, s, kscr);
+    if (rc) return rc;
+    const double* kf = kscr.as<double>();
+    const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
+    return launch_multi_at(net, cond, kf, kr, n, y, n, st, obj, out, s);
 }

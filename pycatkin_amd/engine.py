@@ -420,6 +420,72 @@ class DeviceNetwork:
                                           float(err_max), C.byref(o), _ptr(out['nsteps']), _stream(torch)))
         return out
 
+    def _multi_io(self, n, wr, wy):
+        """(pck_multi_obj, pck_multi_out, output tensors, tensors to keep alive)
+        of drc_multi_at / drc_multi_adjoint: wr [K, NRXN] and / or wy [K, NDYN]."""
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device='cuda')
+        if wr is None and wy is None:
+            raise ValueError('objectives: wr and wy are both None')
+        keep = []
+        K = None
+        for w, cols, name in ((wr, self.NRXN, 'wr'), (wy, self.NDYN, 'wy')):
+            if w is None:
+                keep.append(None)
+                continue
+            w = torch.as_tensor(w, **f64)
+            if w.dim() == 1:
+                w = w[None]
+            if w.dim() != 2 or w.shape[1] != cols or w.shape[0] < 1 or (K is not None and w.shape[0] != K):
+                raise ValueError('objectives: %s has shape %s, expected (K, %d)' % (name, tuple(w.shape), cols))
+            K = int(w.shape[0])
+            keep.append(w.contiguous())
+        ob = L.MultiObj()
+        ob.K, ob.wr, ob.wy = K, _ptr(keep[0]), _ptr(keep[1])
+        R = self.NRXN
+        t = dict(val=torch.empty((K, n), **f64), xi=torch.zeros((K * max(R, 1), n), **f64),
+                 status=torch.empty(n, dtype=torch.int32, device='cuda'),
+                 ostatus=torch.empty((K, n), dtype=torch.int32, device='cuda'))
+        o = L.MultiOut()
+        o.val, o.ld_val, o.xi, o.ld_xi = _ptr(t['val']), n, _ptr(t['xi']), n
+        o.status, o.ostatus, o.ld_os = _ptr(t['status']), _ptr(t['ostatus']), n
+        t['xi'] = t['xi'][:K * R].reshape(K, R, n)
+        return ob, o, t, keep
+
+    def drc_multi_at(self, n, T, p, y, kf, kr, wr=None, wy=None, desc=None, fixc=None, inflow=None, status_in=None):
+        """pck_drc_multi_at: the degree of rate control of K objectives
+        J_m = wr[m] . net + wy[m] . y (wr [K, NRXN], wy [K, NDYN]; either may be
+        None) at the steady states y [NDYN, n], from one factorisation and K
+        adjoint solves; always the group kernels.  Returns dict(val [K, n],
+        xi [K, NRXN, n], status [n], ostatus [K, n])."""
+        torch = self.torch
+        ob, o, out, keep2 = self._multi_io(n, wr, wy)
+        c, keep = self.conditions(n, T, p, desc, fixc, None, inflow)
+        y = torch.as_tensor(y, dtype=torch.float64, device='cuda').reshape(self.NDYN, n).contiguous()
+        kf = torch.as_tensor(kf, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        kr = torch.as_tensor(kr, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        si = None
+        if status_in is not None:
+            si = torch.as_tensor(status_in, dtype=torch.int32, device='cuda').reshape(-1).contiguous()
+            if si.numel() != n:
+                raise ValueError('status_in has %d entries for %d conditions' % (si.numel(), n))
+        L.check(self.lib.pck_drc_multi_at(self.h, C.byref(c), _ptr(kf), _ptr(kr), n, _ptr(y), n, _ptr(si),
+                                          C.byref(ob), C.byref(o), _stream(torch)))
+        return out
+
+    def drc_multi_adjoint(self, n, T, p, y0, wr=None, wy=None, desc=None, fixc=None, inflow=None, **kw):
+        """pck_drc_multi_adjoint: one steady solve (kw as for solve; newton=True
+        is required) and drc_multi_at at its states.  Returns what drc_multi_at
+        returns plus nsteps."""
+        torch = self.torch
+        ob, o, out, keep2 = self._multi_io(n, wr, wy)
+        c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)
+        prm = self.params(**kw)
+        out['nsteps'] = torch.empty(n, dtype=torch.int32, device='cuda')
+        L.check(self.lib.pck_drc_multi_adjoint(self.h, C.byref(c), C.byref(prm), C.byref(ob), C.byref(o),
+                                               _ptr(out['nsteps']), _stream(torch)))
+        return out
+
 
 _form_cache = {}
 
