@@ -463,10 +463,11 @@ typedef struct {
  * gated one get NaN in every xi, and that status in every ostatus.  ostatus[m]:
  * PCK_ST_NONFINITE for a zero or non-finite J_m (or an adjoint solve that overflows):
  * NaN xi[m][:] for that objective alone.  val is written for every condition.
- * Always the 16- / 32- / 64-lane group kernels, whatever pck_network_set_sens_lanes
- * says; pck_network_sens_lanes reports G afterwards.  Sizes as pck_drc_at (PCK_E_SIZE);
- * PCK_E_ARG: K < 1, NULL obj / out / val / xi, wr and wy both NULL, a leading
- * dimension below n. */
+ * The kernel is chosen by pck_network_set_multi_lanes (below), whatever
+ * pck_network_set_sens_lanes says: by default the 16- / 32- / 64-lane group kernels;
+ * pck_network_sens_lanes reports G afterwards, or 1 after a one-lane launch.  Sizes as
+ * pck_drc_at (PCK_E_SIZE); PCK_E_ARG: K < 1, NULL obj / out / val / xi, wr and wy both
+ * NULL, a leading dimension below n. */
 int pck_drc_multi_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
                      int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
                      const pck_multi_obj* obj, const pck_multi_out* out, void* stream);
@@ -479,6 +480,18 @@ int pck_drc_multi_at(const pck_network* net, const pck_conditions* cond, const d
  * trajectory request, and what pck_drc_multi_at refuses. */
 int pck_drc_multi_adjoint(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
                           const pck_multi_obj* obj, const pck_multi_out* out, int32_t* nsteps, void* stream);
+
+/* Lanes per condition of the kernel behind pck_drc_multi_at and pck_drc_multi_adjoint,
+ * a mode of its own beside pck_network_set_sens_lanes (neither changes what the other's
+ * entry points run): PCK_SENS_LANES_GROUP (default: k_multi_adjoint<G>,
+ * csrc/mk_sens_multi.h), PCK_SENS_LANES_ONE (one lane per condition,
+ * csrc/mk_sens_multi_lane.h: the same formulas, statuses and outputs, every step serial
+ * in its lane; networks of up to PCK_MAX_DYN_LANE dynamic species, else PCK_E_SIZE from
+ * this call), PCK_SENS_LANES_AUTO (one lane up to PCK_MAX_DYN_LANE species, else the
+ * group kernels).  Any other mode is PCK_E_ARG.  The two kinds agree to rounding, not
+ * bitwise (sums over reactions and species run in another order); the argument checks
+ * of the two entry points are the same in every mode. */
+int pck_network_set_multi_lanes(pck_network* net, int mode);
 
 /* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
  * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program

@@ -18,7 +18,8 @@ EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_netw
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
             'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
             'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint', 'pck_sens_at', 'pck_sens_adjoint',
-            'pck_network_set_sens_lanes', 'pck_network_sens_lanes', 'pck_drc_multi_at', 'pck_drc_multi_adjoint')
+            'pck_network_set_sens_lanes', 'pck_network_sens_lanes', 'pck_drc_multi_at', 'pck_drc_multi_adjoint',
+            'pck_network_set_multi_lanes')
 
 ABI_VERSION = 10
 
@@ -36,7 +37,7 @@ MAX_DYN, MAX_DYN_LANE, MAX_RXN, MAX_CONS, MAX_TOF = 64, 8, 256, 4, 16
 MAX_PES = 64
 PLAN_AUTO, PLAN_RUNTIME, PLAN_GROUP = 0, 1, 2
 SENS_LANES_GROUP, SENS_LANES_ONE, SENS_LANES_AUTO = 0, 1, 2
-# adjoint_kernel= of the System calls -> pck_network_set_sens_lanes mode
+# adjoint_kernel= of the System calls -> pck_network_set_sens_lanes / pck_network_set_multi_lanes mode
 SENS_LANES_MODES = {'group': SENS_LANES_GROUP, 'lane': SENS_LANES_ONE, 'auto': SENS_LANES_AUTO}
 ST_OK, ST_MAXSTEPS, ST_STEPFAIL, ST_NONFINITE, ST_NEWTON, ST_NEWTON_LOOSE, ST_DRC_MIXED = range(7)
 ST_SENS_SINGULAR = 7
@@ -132,6 +133,7 @@ def load():
     lib.pck_network_set_plan_mode.argtypes = [vp, C.c_int]
     lib.pck_network_set_sens_lanes.argtypes = [vp, C.c_int]
     lib.pck_network_sens_lanes.argtypes = [vp, i32p]
+    lib.pck_network_set_multi_lanes.argtypes = [vp, C.c_int]
     lib.pck_energies.argtypes = [vp, C.POINTER(Conditions), vp, i64, vp]
     lib.pck_rate_constants.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp]
     lib.pck_species_rates.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp]

@@ -638,7 +638,8 @@ class System:
 
     @staticmethod
     def _adjoint_mode(adjoint_kernel):
-        """pck_network_set_sens_lanes' mode of adjoint_kernel = 'group' | 'lane' | 'auto'."""
+        """pck_network_set_sens_lanes' / pck_network_set_multi_lanes' mode of
+        adjoint_kernel = 'group' | 'lane' | 'auto'."""
         if not isinstance(adjoint_kernel, str) or adjoint_kernel not in _L.SENS_LANES_MODES:
             raise ValueError("adjoint_kernel must be 'group', 'lane' or 'auto', not %r" % (adjoint_kernel,))
         return _L.SENS_LANES_MODES[adjoint_kernel]
@@ -744,7 +745,7 @@ class System:
         return out
 
     def drc_objectives_at(self, objectives, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None,
-                          k=None):
+                          k=None, adjoint_kernel='group'):
         """The analytic degree of rate control of several objectives at given
         steady states Y [n_dynamic, n] (plan.dyn order), from one factorisation
         of the steady Jacobian and one adjoint solve per objective
@@ -755,14 +756,21 @@ class System:
         unknown name, a fixed species or an empty objective raises ValueError.
         The objectives are data of the call: the plan without TOF terms serves
         all of them, and changing them never rebuilds a network.  T, p, desc,
-        fix, inflow, status_in and k as in drc_at.
+        fix, inflow, status_in and k as in drc_at.  adjoint_kernel: 'group' (16,
+        32 or 64 lanes per condition, the default), 'lane' (one lane per
+        condition: networks of at most 8 dynamic species, a larger one raises)
+        or 'auto' ('lane' where the network allows it); a choice of its own,
+        independent of drc_at's; the two kernels agree to rounding (DESIGN.md
+        "Multi-objective DRC, one lane").
         Returns dict(labels [K], reactions [R] (every reaction; ghost reactions
         get 0), val [K, n] (the objectives' values), xi [K, R, n]
         (d ln J_m / d ln k_j at fixed K_j), status [n], ostatus [K, n] (3: a
         zero or non-finite objective, NaN xi for it alone))."""
+        mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan((), None)
         labels, wr, wy = self._objectives(plan, objectives)
         net = self.device((), None)
+        net.set_multi_lanes(mode)
         Y = np.asarray(Y, float)
         if Y.ndim == 1:
             Y = Y[:, None]
@@ -775,15 +783,19 @@ class System:
         return self._multi_dict(plan, labels, r, n)
 
     def drc_objectives_batch(self, objectives, T=None, p=None, desc=None, t_end=None, rtol=None, atol=None,
-                             max_steps=200000, y0=None, fix=None, inflow=None, screen='auto'):
+                             max_steps=200000, y0=None, fix=None, inflow=None, screen='auto',
+                             adjoint_kernel='group'):
         """drc_objectives_at at the steady states of one steady solve per
         condition (pck_drc_multi_adjoint): the arguments of
         drc_batch(steady=True, method='analytic').  A condition whose solve did
-        not report a reached root keeps that status and gets NaN xi.  Returns
-        what drc_objectives_at returns plus 'nsteps'."""
+        not report a reached root keeps that status and gets NaN xi.
+        adjoint_kernel: as in drc_objectives_at.  Returns what
+        drc_objectives_at returns plus 'nsteps'."""
+        mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan((), None)
         labels, wr, wy = self._objectives(plan, objectives)
         net = self.device((), None)
+        net.set_multi_lanes(mode)
         n = self._n(T, p, *(desc.values() if desc else []))
         for a in (y0, fix, inflow):
             if a is not None and np.ndim(a) == 2:
@@ -814,7 +826,8 @@ class System:
         xi_num - xi_den, with r_num and r_den sums of net rates (reaction names
         as tof_terms): the two objectives of one launch, so one factorisation.
         kw as for drc_objectives_batch; with Y (and optionally k, status_in),
-        at those states as drc_objectives_at.
+        at those states as drc_objectives_at.  adjoint_kernel = 'group' |
+        'lane' | 'auto' (in kw) chooses the kernel as in drc_objectives_at.
         Returns dict(reactions [R], dsc [R, n], selectivity [n], status [n] (the
         condition's, or 3 where either rate is zero or not finite), xi_num,
         xi_den [R, n], val_num, val_den [n])."""
@@ -830,8 +843,8 @@ class System:
         """Degree of coverage control d ln y_i / d ln k_j of the dynamic species
         `species` (None: every dynamic species, plan.dyn order) -- for a CSTR's
         gas species the control of its outlet concentration: len(species)
-        objectives of one launch.  kw, Y, k, status_in as in
-        selectivity_control_batch.
+        objectives of one launch.  kw (adjoint_kernel = 'group' | 'lane' |
+        'auto' among them), Y, k, status_in as in selectivity_control_batch.
         Returns dict(species, reactions [R], dcc [len(species), R, n], coverage
         [len(species), n], status [n], ostatus [len(species), n] (3: a species
         at exactly 0, NaN dcc for it alone))."""

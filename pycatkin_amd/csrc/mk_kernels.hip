@@ -48,6 +48,7 @@ struct pck_network {
     mutable std::atomic<bool> grp_quad_on{false}; // ... the quad-group kernel (mk_quad.h)
     mutable std::atomic<int> grp_lanes{0};        // lanes per condition of the last lane-group solve
     int sens_mode = PCK_SENS_LANES_GROUP;         // pck_network_set_sens_lanes
+    int multi_mode = PCK_SENS_LANES_GROUP;        // pck_network_set_multi_lanes
     mutable std::atomic<int> sens_lanes{0};       // lanes per condition of the last adjoint launch
 };
 
@@ -263,6 +264,7 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 #include "mk_sens.h"
 #include "mk_sens_lane.h"
 #include "mk_sens_multi.h"
+#include "mk_sens_multi_lane.h"
 
 // The solver kernels are compiled in translation units of their own in the
 // product build (csrc/mk_inst.h, csrc/tu_*.hip): here they are only declared.
@@ -676,6 +678,16 @@ extern "C" int pck_network_set_sens_lanes(pck_network* net, int mode) {
     if (mode == PCK_SENS_LANES_ONE && net->nv.NDYN > PCK_MAX_DYN_LANE)
         return fail(PCK_E_SIZE, "one-lane adjoint: at most %s%lld dynamic species", "", PCK_MAX_DYN_LANE);
     net->sens_mode = mode;
+    return PCK_OK;
+}
+
+extern "C" int pck_network_set_multi_lanes(pck_network* net, int mode) {
+    if (!net) return fail(PCK_E_ARG, "null network%s", "");
+    if (mode < PCK_SENS_LANES_GROUP || mode > PCK_SENS_LANES_AUTO)
+        return fail(PCK_E_ARG, "unknown multi-objective lane mode%s %lld", "", mode);
+    if (mode == PCK_SENS_LANES_ONE && net->nv.NDYN > PCK_MAX_DYN_LANE)
+        return fail(PCK_E_SIZE, "one-lane multi-objective DRC: at most %s%lld dynamic species", "", PCK_MAX_DYN_LANE);
+    net->multi_mode = mode;
     return PCK_OK;
 }
 
@@ -1730,19 +1742,34 @@ static int check_multi(const pck_network* net, int64_t n, const pck_multi_obj* o
     return PCK_OK;
 }
 
-// always the group kernels, whatever pck_network_set_sens_lanes says; the checks of check_multi are done
+// the group kernels, or one lane per condition (csrc/mk_sens_multi_lane.h), by the network's mode of its own
+// (pck_network_set_multi_lanes), whatever pck_network_set_sens_lanes says; the checks of check_multi are done
 static int launch_multi_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
                            int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
                            const pck_multi_obj* obj, const pck_multi_out* out, hipStream_t s) {
     const int64_t n = cond->n;
     if (n == 0) return PCK_OK;
+    const MultiObj ob{obj->K, obj->wr, obj->wy};
+    const MultiOut mo{out->val, out->ld_val, out->xi, out->ld_xi, out->status, out->ostatus, out->ld_os};
+    if (net->multi_mode != PCK_SENS_LANES_GROUP && net->nv.NDYN <= PCK_MAX_DYN_LANE) {
+        const int64_t nbl = (n + 63) / 64;
+        if (nbl > 0x7fffffffLL) return fail(PCK_E_SIZE, "multi-objective DRC: more than 2^31 - 1 workgroups%s", "");
+        // 24 KiB at NS 4, 80 KiB at 8: above the 64 KiB a kernel may ask for by default its limit is raised
+        const size_t shml = multi_lane_lds_bytes(net->nv.NDYN);
+        if (shml > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)k_lane_multi_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)shml));
+        hipLaunchKernelGGL(k_lane_multi_adjoint, dim3((unsigned)nbl), dim3(64), shml, s, net->nv, net->gv, cview(cond),
+                           kf, kr, ld_k, y, ld_y, status_in, ob, mo);
+        HIPCHK(hipGetLastError());
+        net->sens_lanes.store(1, std::memory_order_relaxed);
+        return PCK_OK;
+    }
     const int G = grp_g(net->nv.NDYN), per = 64 / G;
     const int64_t nb = (n + per - 1) / per;
     if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "multi-objective DRC: more than 2^31 - 1 workgroups%s", "");
     const dim3 g((unsigned)nb);
     const size_t shm = multi_lds_bytes(G);         // 17 / 33 / 65 KiB
-    const MultiObj ob{obj->K, obj->wr, obj->wy};
-    const MultiOut mo{out->val, out->ld_val, out->xi, out->ld_xi, out->status, out->ostatus, out->ld_os};
     // above the 64 KiB a kernel may ask for by default its limit is raised (a CU has 160 KiB)
 #define CALL(GG)                                                                                                     \
     do {                                                                                                             \

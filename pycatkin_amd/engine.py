@@ -81,6 +81,14 @@ class DeviceNetwork:
         it, else the group kernels (pck_network_set_sens_lanes)."""
         L.check(self.lib.pck_network_set_sens_lanes(self.h, int(mode)))
 
+    def set_multi_lanes(self, mode):
+        """Lanes per condition of the multi-objective kernels (drc_multi_at,
+        drc_multi_adjoint), modes as set_sens_lanes and independent of it: 0 =
+        the group kernels (the default), 1 = one lane per condition (up to 8
+        dynamic species; a larger network raises), 2 = one lane where the
+        network allows it (pck_network_set_multi_lanes)."""
+        L.check(self.lib.pck_network_set_multi_lanes(self.h, int(mode)))
+
     def sens_lanes(self):
         """Lanes per condition of the last adjoint launch: 1, 16, 32 or 64; 0
         before any."""
@@ -456,7 +464,7 @@ class DeviceNetwork:
         """pck_drc_multi_at: the degree of rate control of K objectives
         J_m = wr[m] . net + wy[m] . y (wr [K, NRXN], wy [K, NDYN]; either may be
         None) at the steady states y [NDYN, n], from one factorisation and K
-        adjoint solves; always the group kernels.  Returns dict(val [K, n],
+        adjoint solves; the kernel by set_multi_lanes.  Returns dict(val [K, n],
         xi [K, NRXN, n], status [n], ostatus [K, n])."""
         torch = self.torch
         ob, o, out, keep2 = self._multi_io(n, wr, wy)

@@ -7,6 +7,7 @@ process.
   syn24     the 64 conditions of tests/golden/synthetic_sizes_fixture.npz tiled
             to 4 096 (24 species, 72 reactions)
   volcano   the 1024 x 1024 COOx volcano grid at 600 K
+  cstr      the Pd111 CSTR at 10 000 temperatures 423-623 K
 
 Per workload one steady solve gives the states; then, each a kernel alone at
 those states on the current stream:
@@ -14,13 +15,18 @@ those states on the current stream:
   K1        pck_drc_multi_at, the same TOF terms as the one objective
   K2        ... and a second rate objective (the first TOF term alone)
   KNS       every dynamic species as a coverage objective (K = NS)
+On a network of at most 8 dynamic species (volcano, cstr) K1 / K2 / KNS are
+also timed on the one-lane kernel (csrc/mk_sens_multi_lane.h:
+k_lane_multi_adjoint, pck_network_set_multi_lanes) as lane_K1 / lane_K2 /
+lane_KNS, beside the group kernel in the same rounds.
 
 HIP events around `reps` back-to-back calls, the median of `--rounds` rounds
-with the spread; the rounds interleave the four.  Prints one JSON line per
-workload with the K = 1 time over drc_at's and the increment per objective,
-(KNS - K1) / (NS - 1).  Needs the GPU.
+with the spread; the rounds interleave all of them.  Prints one JSON line per
+workload with the K = 1 time over drc_at's, the increment per objective,
+(KNS - K1) / (NS - 1), and for the one-lane kernel group over lane per K and
+the worst |xi_lane - xi_group| over the answered conditions.  Needs the GPU.
 
-    python tools/drc_multi_bench.py [--workloads dmtm,syn24,volcano] [--rounds 5]
+    python tools/drc_multi_bench.py [--workloads dmtm,syn24,volcano,cstr] [--rounds 5]
 """
 import argparse
 import json
@@ -60,13 +66,19 @@ def run(name, sim, terms, kw, n, a, torch):
     def drc_at():
         state['at'] = net.drc_at(n, T, p, y, kf, kr, d, fx, inflow, st)
 
-    def multi(key, wr, wy):
+    def multi(key, wr, wy, mode=0):
         def fn():
+            net0.set_multi_lanes(mode)
             state[key] = net0.drc_multi_at(n, T, p, y, kf, kr, wr, wy, d, fx, inflow, st)
+            state[key + '_lanes'] = net0.sens_lanes()
         return fn
 
     todo = [('drc_at', drc_at), ('K1', multi('K1', wr1, None)), ('K2', multi('K2', wr2, None)),
             ('KNS', multi('KNS', None, wyn))]
+    one_lane = NS <= 8
+    if one_lane:
+        todo += [('lane_K1', multi('lane_K1', wr1, None, 1)), ('lane_K2', multi('lane_K2', wr2, None, 1)),
+                 ('lane_KNS', multi('lane_KNS', None, wyn, 1))]
 
     def timed(fn, reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -84,7 +96,8 @@ def run(name, sim, terms, kw, n, a, torch):
     for _ in range(a.rounds):
         for k, fn in todo:
             ms[k].append(timed(fn, a.reps))
-    res = dict(workload=name, conditions=n, species=NS, reactions=R, lanes=net0.sens_lanes())
+    net0.set_multi_lanes(0)
+    res = dict(workload=name, conditions=n, species=NS, reactions=R, lanes=state['K1_lanes'])
     for k, v in ms.items():
         res[k + '_ms'] = round(float(np.median(v)), 4)
         res[k + '_ms_min_max'] = [round(float(min(v)), 4), round(float(max(v)), 4)]
@@ -96,6 +109,15 @@ def run(name, sim, terms, kw, n, a, torch):
     res['status_counts'] = {int(k): int(v) for k, v in zip(*np.unique(state['K1']['status'].cpu().numpy(),
                                                                       return_counts=True))}
     res['K1_minus_drc_at_worst'] = float((xa - xm).abs().max()) if bool(ok.any()) else None
+    if one_lane:
+        assert state['lane_K1_lanes'] == 1 and state['K1_lanes'] > 1
+        for k in ('K1', 'K2', 'KNS'):
+            res['group_over_lane_' + k] = round(res[k + '_ms'] / res['lane_' + k + '_ms'], 3)
+            g, l = state[k], state['lane_' + k]
+            assert bool((g['status'] == l['status']).all()) and bool((g['ostatus'] == l['ostatus']).all())
+            both = (g['ostatus'] == 0).unsqueeze(1).expand_as(g['xi'])
+            dx = (g['xi'] - l['xi'])[both]
+            res['lane_minus_group_worst_' + k] = float(dx.abs().max()) if dx.numel() else None
     print(json.dumps(res), flush=True)
 
 
@@ -105,15 +127,17 @@ def main():
     ap.add_argument('--dmtm-grid', type=int, default=64)
     ap.add_argument('--volcano-grid', type=int, default=1024)
     ap.add_argument('--syn24-n', type=int, default=4096)
+    ap.add_argument('--cstr-n', type=int, default=10000)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--reps', type=int, default=3)
     a = ap.parse_args()
     import torch
     import pycatkin_amd as P
     from drc_adjoint_bench import dmtm, syn24, volcano
-    size = dict(dmtm=a.dmtm_grid, volcano=a.volcano_grid, syn24=a.syn24_n)
+    from sens_adjoint_bench import cstr
+    size = dict(dmtm=a.dmtm_grid, volcano=a.volcano_grid, syn24=a.syn24_n, cstr=a.cstr_n)
     for name in a.workloads.split(','):
-        sim, terms, kw, n = dict(dmtm=dmtm, volcano=volcano, syn24=syn24)[name](P, size[name])
+        sim, terms, kw, n = dict(dmtm=dmtm, volcano=volcano, syn24=syn24, cstr=cstr)[name](P, size[name])
         run(name, sim, terms, kw, n, a, torch)
 
 
