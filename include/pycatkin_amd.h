@@ -409,8 +409,8 @@ int pck_sens_adjoint(const pck_network* net, const pck_conditions* cond, const p
 
 /* Lanes per condition of the adjoint kernels behind pck_drc_at, pck_drc_adjoint,
  * pck_sens_at and pck_sens_adjoint: PCK_SENS_LANES_GROUP (default: G = 16, 32 or 64
- * lanes own one condition, csrc/mk_sens.h), PCK_SENS_LANES_ONE (one lane per
- * condition, csrc/mk_sens_lane.h: the same formulas, statuses and outputs, every
+ * lanes own one condition, csrc/mk_sens.h over the steps of csrc/mk_adjoint.h),
+ * PCK_SENS_LANES_ONE (one lane per condition, csrc/mk_sens_lane.h: the same formulas, statuses and outputs, every
  * step serial in its lane; networks of up to PCK_MAX_DYN_LANE dynamic species, else
  * PCK_E_SIZE from this call), PCK_SENS_LANES_AUTO (one lane up to PCK_MAX_DYN_LANE
  * species, else the group kernels).  Any other mode is PCK_E_ARG.  The two kinds
@@ -452,7 +452,8 @@ typedef struct {
  * pck_drc_at's assembly and equilibration, one LU factorisation whose multipliers are
  * kept, and per objective one adjoint solve on the stored factors,
  *   A^T lambda_m = dJ_m/dy,   xi[m][j] = net_j (wr[m][j] - sum_i lambda_mi w_i S_ij) / J_m
- * (w_i the row scale, 0 on a replaced row), double-double throughout (csrc/mk_sens_multi.h).
+ * (w_i the row scale, 0 on a replaced row), double-double throughout (csrc/mk_sens_multi.h;
+ * assembly, LU and solve in csrc/mk_adjoint.h).
  * xi_num - xi_den is the control of the selectivity J_num / J_den; a coverage
  * objective gives d ln theta_i / d ln k_j.  Only val and xi: the per-direction
  * split, reaction orders and user directions of pck_sens_at are not offered per

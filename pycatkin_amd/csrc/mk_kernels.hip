@@ -1520,18 +1520,93 @@ extern "C" int pck_drc(const pck_network* net, const pck_conditions* cond, const
 }
 
 // ----------------------------------------------------------------------------
+// the adjoint kernels (csrc/mk_sens*.h over csrc/mk_adjoint.h): what their entry points share
+// ----------------------------------------------------------------------------
+// the network's limits; `what` leads every message
+static int check_adjoint_net(const pck_network* net, const char* what, bool need_tof) {
+    const int NS = net->nv.NDYN;
+    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "%s: 1..%lld dynamic species", what, PCK_MAX_DYN);
+    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "%s: 1..%lld reactions", what, PCK_MAX_RXN);
+    if (!net->grp_ok) {                            // two strings: fail() formats one string and one integer
+        char msg[sizeof(g_err)];
+        snprintf(msg, sizeof(msg), "%s (record tables): %s", what, net->grp_why);
+        return fail(PCK_E_SIZE, "%s", msg);
+    }
+    if (need_tof && net->nv.NTOF < 1) return fail(PCK_E_ARG, "%s: the network has no TOF terms", what);
+    return PCK_OK;
+}
+
+// `per` conditions per block of 64 lanes, `shm` bytes of dynamic LDS: above the 64 KiB a kernel may ask for by
+// default its limit is raised (a CU has 160 KiB)
+template <class K, class... A>
+static int launch_adjoint(K kernel, int per, size_t shm, const pck_network* net, int64_t n, const char* what,
+                          hipStream_t s, A... args) {
+    const int64_t nb = (n + per - 1) / per;
+    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "%s: more than 2^31 - 1 workgroups", what);
+    if (shm > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(64), shm, s, net->nv, net->gv, args...);
+    HIPCHK(hipGetLastError());
+    net->sens_lanes.store(64 / per, std::memory_order_relaxed);
+    return PCK_OK;
+}
+// one lane per condition: LDS by NS, 24 KiB at NS 4, 80 KiB at 8 (sens_lane_lds_bytes; multi_lane_lds_bytes is
+// the same 16 (NS^2 + 2 NS) 64 bytes)
+template <class K, class... A>
+static int launch_adjoint_lane(K kernel, const pck_network* net, int64_t n, const char* what, hipStream_t s, A... args) {
+    return launch_adjoint(kernel, 64, sens_lane_lds_bytes(net->nv.NDYN), net, n, what, s, args...);
+}
+// G = grp_g(NS) lanes per condition (the group schedule); lds: sens_lds_bytes (16 / 32 / 64 KiB) or
+// multi_lds_bytes (17 / 33 / 65 KiB)
+template <class K, class... A>
+static int launch_adjoint_group(K k16, K k32, K k64, size_t (*lds)(int), const pck_network* net, int64_t n,
+                                const char* what, hipStream_t s, A... args) {
+    const int G = grp_g(net->nv.NDYN);
+    return launch_adjoint(G == 16 ? k16 : G == 32 ? k32 : k64, 64 / G, lds(G), net, n, what, s, args...);
+}
+
+// The steady solve in front of an adjoint solve at its states (pck_*_adjoint).
+// `who` names the entry point: Newton, no trajectory.
+static int check_adjoint_params(const pck_solve_params* prm, const char* who) {
+    const int rc = check_params(prm);
+    if (rc) return rc;
+    if (!prm->newton) return fail(PCK_E_ARG, "%s needs newton = 1: a transient end has no implicit-function sensitivity", who);
+    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "%s takes no trajectory request (t_out)", who);
+    return PCK_OK;
+}
+struct SteadyStates {
+    StreamScratch yscr;                            // y | status, sized by the batch
+    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
+    const double* kf; const double* kr;
+    double* y; int32_t* st;
+};
+static int solve_steady(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                        int32_t* nsteps, hipStream_t s, SteadyStates& o) {
+    const int64_t n = cond->n;
+    const int NS = net->nv.NDYN, R = net->nv.NRXN;
+    int rc = salloc(o.yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    if (rc) return rc;
+    o.y = o.yscr.as<double>();
+    o.st = (int32_t*)(o.y + (int64_t)NS * n);
+    pck_solve_params p = *prm;
+    p.want_activity = 0;
+    SolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = o.y; a.ld_y = n; a.tof = nullptr; a.status = o.st; a.nsteps = nsteps;
+    a.G = 1;
+    rc = launch_solve(net, cond, &p, a, s, o.kscr);
+    if (rc) return rc;
+    o.kf = o.kscr.as<double>();
+    o.kr = o.kf + (int64_t)(R > 0 ? R : 1) * n;
+    return PCK_OK;
+}
+
+// ----------------------------------------------------------------------------
 // analytic DRC (csrc/mk_sens.h)
 // ----------------------------------------------------------------------------
 // one lane per condition (csrc/mk_sens_lane.h) by the network's mode (pck_network_set_sens_lanes)
 static inline bool sens_one_lane(const pck_network* net) {
     return net->sens_mode != PCK_SENS_LANES_GROUP && net->nv.NDYN <= PCK_MAX_DYN_LANE;
-}
-// dynamic LDS of a one-lane launch, sized by NS: 24 KiB at NS 4, 80 KiB at 8.
-// Above the 64 KiB a kernel may ask for by default its limit is raised (a CU has 160 KiB).
-static int sens_lane_lds(const void* kernel, int NS, size_t* shm) {
-    *shm = sens_lane_lds_bytes(NS);
-    if (*shm > 64 * 1024) HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*shm));
-    return PCK_OK;
 }
 
 static int launch_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
@@ -1539,36 +1614,14 @@ static int launch_drc_at(const pck_network* net, const pck_conditions* cond, con
                          int64_t ld_xi, double* tof0, int32_t* status, hipStream_t s) {
     const int64_t n = cond->n;
     if (n == 0) return PCK_OK;
-    const int NS = net->nv.NDYN;
-    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "analytic DRC: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
-    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "analytic DRC: 1..%s%lld reactions", "", PCK_MAX_RXN);
-    if (!net->grp_ok) return fail(PCK_E_SIZE, "analytic DRC (record tables): %s", net->grp_why);
-    if (net->nv.NTOF < 1) return fail(PCK_E_ARG, "analytic DRC: the network has no TOF terms%s", "");
-    if (sens_one_lane(net)) {                      // csrc/mk_sens_lane.h
-        const int64_t nbl = (n + 63) / 64;
-        if (nbl > 0x7fffffffLL) return fail(PCK_E_SIZE, "analytic DRC: more than 2^31 - 1 workgroups%s", "");
-        size_t shml = 0;
-        const int rc = sens_lane_lds((const void*)k_lane_drc_adjoint, NS, &shml);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_lane_drc_adjoint, dim3((unsigned)nbl), dim3(64), shml, s, net->nv, net->gv, cview(cond), kf,
-                           kr, ld_k, y, ld_y, status_in, xi, ld_xi, tof0, status);
-        HIPCHK(hipGetLastError());
-        net->sens_lanes.store(1, std::memory_order_relaxed);
-        return PCK_OK;
-    }
-    const int G = grp_g(NS), per = 64 / G;
-    const int64_t nb = (n + per - 1) / per;
-    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "analytic DRC: more than 2^31 - 1 workgroups%s", "");
-    const dim3 g((unsigned)nb);
-    const size_t shm = sens_lds_bytes(G);          // 16 / 32 / 64 KiB
-#define CALL(GG) hipLaunchKernelGGL((k_drc_adjoint<GG>), g, dim3(64), shm, s, net->nv, net->gv, cview(cond), kf, kr, ld_k, y, ld_y, status_in, xi, ld_xi, tof0, status)
-    if (G == 16) CALL(16);
-    else if (G == 32) CALL(32);
-    else CALL(64);
-#undef CALL
-    HIPCHK(hipGetLastError());
-    net->sens_lanes.store(G, std::memory_order_relaxed);
-    return PCK_OK;
+    const char* what = "analytic DRC";
+    const int rc = check_adjoint_net(net, what, true);
+    if (rc) return rc;
+    if (sens_one_lane(net))
+        return launch_adjoint_lane(k_lane_drc_adjoint, net, n, what, s, cview(cond), kf, kr, ld_k, y, ld_y, status_in, xi,
+                                   ld_xi, tof0, status);
+    return launch_adjoint_group(k_drc_adjoint<16>, k_drc_adjoint<32>, k_drc_adjoint<64>, sens_lds_bytes, net, n, what, s,
+                                cview(cond), kf, kr, ld_k, y, ld_y, status_in, xi, ld_xi, tof0, status);
 }
 
 // the adjoint sensitivities (csrc/mk_sens.h: k_sens_adjoint); the checks of launch_drc_at
@@ -1576,13 +1629,11 @@ static int launch_sens_at(const pck_network* net, const pck_conditions* cond, co
                           int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in,
                           const pck_sens_dirs* dirs, double err_max, const pck_sens_out* out, hipStream_t s) {
     const int64_t n = cond->n;
+    const char* what = "adjoint sensitivities";
     if (!out) return fail(PCK_E_ARG, "adjoint sensitivities: no outputs%s", "");
     if (n == 0) return PCK_OK;
-    const int NS = net->nv.NDYN;
-    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "adjoint sensitivities: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
-    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "adjoint sensitivities: 1..%s%lld reactions", "", PCK_MAX_RXN);
-    if (!net->grp_ok) return fail(PCK_E_SIZE, "adjoint sensitivities (record tables): %s", net->grp_why);
-    if (net->nv.NTOF < 1) return fail(PCK_E_ARG, "adjoint sensitivities: the network has no TOF terms%s", "");
+    const int rc = check_adjoint_net(net, what, true);
+    if (rc) return rc;
     if ((out->xi && out->ld_xi < n) || ((out->sf || out->sr) && out->ld_s < n) || (out->order && out->ld_order < n) ||
         (out->order_in && out->ld_in < n))
         return fail(PCK_E_ARG, "adjoint sensitivities: a leading dimension of pck_sens_out is below n%s", "");
@@ -1600,31 +1651,12 @@ static int launch_sens_at(const pck_network* net, const pck_conditions* cond, co
         ex.a = dirs->a; ex.c = dirs->c; ex.ld_ac = dirs->ld; ex.s_ac = dirs->stride; ex.nd = (int)dirs->nd;
         ex.dir = out->dir; ex.ld_dir = out->ld_dir;
     }
-    if (sens_one_lane(net)) {                      // csrc/mk_sens_lane.h
-        const int64_t nbl = (n + 63) / 64;
-        if (nbl > 0x7fffffffLL) return fail(PCK_E_SIZE, "adjoint sensitivities: more than 2^31 - 1 workgroups%s", "");
-        size_t shml = 0;
-        const int rc = sens_lane_lds((const void*)k_lane_sens_adjoint, NS, &shml);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_lane_sens_adjoint, dim3((unsigned)nbl), dim3(64), shml, s, net->nv, net->gv, cview(cond), kf,
-                           kr, ld_k, y, ld_y, status_in, out->xi, out->ld_xi, out->tof0, out->status, ex);
-        HIPCHK(hipGetLastError());
-        net->sens_lanes.store(1, std::memory_order_relaxed);
-        return PCK_OK;
-    }
-    const int G = grp_g(NS), per = 64 / G;
-    const int64_t nb = (n + per - 1) / per;
-    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "adjoint sensitivities: more than 2^31 - 1 workgroups%s", "");
-    const dim3 g((unsigned)nb);
-    const size_t shm = sens_lds_bytes(G);          // 16 / 32 / 64 KiB
-#define CALL(GG) hipLaunchKernelGGL((k_sens_adjoint<GG>), g, dim3(64), shm, s, net->nv, net->gv, cview(cond), kf, kr, ld_k, y, ld_y, status_in, out->xi, out->ld_xi, out->tof0, out->status, ex)
-    if (G == 16) CALL(16);
-    else if (G == 32) CALL(32);
-    else CALL(64);
-#undef CALL
-    HIPCHK(hipGetLastError());
-    net->sens_lanes.store(G, std::memory_order_relaxed);
-    return PCK_OK;
+    if (sens_one_lane(net))
+        return launch_adjoint_lane(k_lane_sens_adjoint, net, n, what, s, cview(cond), kf, kr, ld_k, y, ld_y, status_in,
+                                   out->xi, out->ld_xi, out->tof0, out->status, ex);
+    return launch_adjoint_group(k_sens_adjoint<16>, k_sens_adjoint<32>, k_sens_adjoint<64>, sens_lds_bytes, net, n, what,
+                                s, cview(cond), kf, kr, ld_k, y, ld_y, status_in, out->xi, out->ld_xi, out->tof0,
+                                out->status, ex);
 }
 
 // d TOF / d theta = dTOF/dtheta|_y - lambda . dF/dtheta|_y at given states: reaction
@@ -1645,33 +1677,16 @@ extern "C" int pck_sens_adjoint(const pck_network* net, const pck_conditions* co
                                 int32_t* nsteps, void* stream) {
     int rc = check_cond(net, cond, true);
     if (rc) return rc;
-    rc = check_params(prm);
+    rc = check_adjoint_params(prm, "pck_sens_adjoint");
     if (rc) return rc;
-    if (!prm->newton)
-        return fail(PCK_E_ARG, "pck_sens_adjoint needs newton = 1: a transient end has no implicit-function sensitivity%s", "");
-    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "pck_sens_adjoint takes no trajectory request (t_out)%s", "");
     if (!out) return fail(PCK_E_ARG, "adjoint sensitivities: no outputs%s", "");
     const int64_t n = cond->n;
     if (n == 0) return PCK_OK;
     const hipStream_t s = (hipStream_t)stream;
-    const int NS = net->nv.NDYN, R = net->nv.NRXN;
-    StreamScratch yscr;                            // the solve's states and statuses
-    rc = salloc(yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    SteadyStates ss;
+    rc = solve_steady(net, cond, prm, nsteps, s, ss);
     if (rc) return rc;
-    double* y = yscr.as<double>();
-    int32_t* st = (int32_t*)(y + (int64_t)NS * n);
-    pck_solve_params p = *prm;
-    p.want_activity = 0;
-    SolveArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y = y; a.ld_y = n; a.tof = nullptr; a.status = st; a.nsteps = nsteps;
-    a.G = 1;
-    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
-    rc = launch_solve(net, cond, &p, a, s, kscr);
-    if (rc) return rc;
-    const double* kf = kscr.as<double>();
-    const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
-    return launch_sens_at(net, cond, kf, kr, n, y, n, st, dirs, err_max, out, s);
+    return launch_sens_at(net, cond, ss.kf, ss.kr, n, ss.y, n, ss.st, dirs, err_max, out, s);
 }
 
 // System.degree_of_rate_control (old_system.py:490) in the limit eps -> 0, at
@@ -1694,34 +1709,16 @@ extern "C" int pck_drc_adjoint(const pck_network* net, const pck_conditions* con
                                void* stream) {
     int rc = check_cond(net, cond, true);
     if (rc) return rc;
-    rc = check_params(prm);
+    rc = check_adjoint_params(prm, "pck_drc_adjoint");
     if (rc) return rc;
-    if (!prm->newton)
-        return fail(PCK_E_ARG, "pck_drc_adjoint needs newton = 1: a transient end has no implicit-function sensitivity%s", "");
-    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "pck_drc_adjoint takes no trajectory request (t_out)%s", "");
     const int64_t n = cond->n;
     if (n > 0 && (!xi || ld_xi < n)) return fail(PCK_E_ARG, "bad xi output%s", "");
     if (n == 0) return PCK_OK;
     const hipStream_t s = (hipStream_t)stream;
-    const int NS = net->nv.NDYN, R = net->nv.NRXN;
-    // the solve's states and statuses: sized by the batch
-    StreamScratch yscr;
-    rc = salloc(yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    SteadyStates ss;
+    rc = solve_steady(net, cond, prm, nsteps, s, ss);
     if (rc) return rc;
-    double* y = yscr.as<double>();
-    int32_t* st = (int32_t*)(y + (int64_t)NS * n);
-    pck_solve_params p = *prm;
-    p.want_activity = 0;
-    SolveArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y = y; a.ld_y = n; a.tof = nullptr; a.status = st; a.nsteps = nsteps;
-    a.G = 1;
-    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
-    rc = launch_solve(net, cond, &p, a, s, kscr);
-    if (rc) return rc;
-    const double* kf = kscr.as<double>();
-    const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
-    return launch_drc_at(net, cond, kf, kr, n, y, n, st, xi, ld_xi, tof0, status, s);
+    return launch_drc_at(net, cond, ss.kf, ss.kr, n, ss.y, n, ss.st, xi, ld_xi, tof0, status, s);
 }
 
 // ----------------------------------------------------------------------------
@@ -1735,11 +1732,7 @@ static int check_multi(const pck_network* net, int64_t n, const pck_multi_obj* o
     if (!out->val || !out->xi) return fail(PCK_E_ARG, "multi-objective DRC: val and xi are required%s", "");
     if (out->ld_val < n || out->ld_xi < n || (out->ostatus && out->ld_os < n))
         return fail(PCK_E_ARG, "multi-objective DRC: a leading dimension of pck_multi_out is below n%s", "");
-    const int NS = net->nv.NDYN;
-    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "multi-objective DRC: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
-    if (net->nv.NRXN < 1 || net->nv.NRXN > PCK_MAX_RXN) return fail(PCK_E_SIZE, "multi-objective DRC: 1..%s%lld reactions", "", PCK_MAX_RXN);
-    if (!net->grp_ok) return fail(PCK_E_SIZE, "multi-objective DRC (record tables): %s", net->grp_why);
-    return PCK_OK;
+    return check_adjoint_net(net, "multi-objective DRC", false);
 }
 
 // the group kernels, or one lane per condition (csrc/mk_sens_multi_lane.h), by the network's mode of its own
@@ -1749,43 +1742,14 @@ static int launch_multi_at(const pck_network* net, const pck_conditions* cond, c
                            const pck_multi_obj* obj, const pck_multi_out* out, hipStream_t s) {
     const int64_t n = cond->n;
     if (n == 0) return PCK_OK;
+    const char* what = "multi-objective DRC";
     const MultiObj ob{obj->K, obj->wr, obj->wy};
     const MultiOut mo{out->val, out->ld_val, out->xi, out->ld_xi, out->status, out->ostatus, out->ld_os};
-    if (net->multi_mode != PCK_SENS_LANES_GROUP && net->nv.NDYN <= PCK_MAX_DYN_LANE) {
-        const int64_t nbl = (n + 63) / 64;
-        if (nbl > 0x7fffffffLL) return fail(PCK_E_SIZE, "multi-objective DRC: more than 2^31 - 1 workgroups%s", "");
-        // 24 KiB at NS 4, 80 KiB at 8: above the 64 KiB a kernel may ask for by default its limit is raised
-        const size_t shml = multi_lane_lds_bytes(net->nv.NDYN);
-        if (shml > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)k_lane_multi_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)shml));
-        hipLaunchKernelGGL(k_lane_multi_adjoint, dim3((unsigned)nbl), dim3(64), shml, s, net->nv, net->gv, cview(cond),
-                           kf, kr, ld_k, y, ld_y, status_in, ob, mo);
-        HIPCHK(hipGetLastError());
-        net->sens_lanes.store(1, std::memory_order_relaxed);
-        return PCK_OK;
-    }
-    const int G = grp_g(net->nv.NDYN), per = 64 / G;
-    const int64_t nb = (n + per - 1) / per;
-    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "multi-objective DRC: more than 2^31 - 1 workgroups%s", "");
-    const dim3 g((unsigned)nb);
-    const size_t shm = multi_lds_bytes(G);         // 17 / 33 / 65 KiB
-    // above the 64 KiB a kernel may ask for by default its limit is raised (a CU has 160 KiB)
-#define CALL(GG)                                                                                                     \
-    do {                                                                                                             \
-        if (shm > 64 * 1024)                                                                                         \
-            HIPCHK(hipFuncSetAttribute((const void*)k_multi_adjoint<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       (int)shm));                                                                   \
-        hipLaunchKernelGGL((k_multi_adjoint<GG>), g, dim3(64), shm, s, net->nv, net->gv, cview(cond), kf, kr, ld_k, y, \
-                           ld_y, status_in, ob, mo);                                                                 \
-    } while (0)
-    if (G == 16) CALL(16);
-    else if (G == 32) CALL(32);
-    else CALL(64);
-#undef CALL
-    HIPCHK(hipGetLastError());
-    net->sens_lanes.store(G, std::memory_order_relaxed);
-    return PCK_OK;
+    if (net->multi_mode != PCK_SENS_LANES_GROUP && net->nv.NDYN <= PCK_MAX_DYN_LANE)
+        return launch_adjoint_lane(k_lane_multi_adjoint, net, n, what, s, cview(cond), kf, kr, ld_k, y, ld_y, status_in, ob,
+                                   mo);
+    return launch_adjoint_group(k_multi_adjoint<16>, k_multi_adjoint<32>, k_multi_adjoint<64>, multi_lds_bytes, net, n,
+                                what, s, cview(cond), kf, kr, ld_k, y, ld_y, status_in, ob, mo);
 }
 
 // d ln J_m / d ln k_j at given steady states for K objectives J_m that are data of
@@ -1808,32 +1772,15 @@ extern "C" int pck_drc_multi_adjoint(const pck_network* net, const pck_condition
                                      void* stream) {
     int rc = check_cond(net, cond, true);
     if (rc) return rc;
-    rc = check_params(prm);
+    rc = check_adjoint_params(prm, "pck_drc_multi_adjoint");
     if (rc) return rc;
-    if (!prm->newton)
-        return fail(PCK_E_ARG, "pck_drc_multi_adjoint needs newton = 1: a transient end has no implicit-function sensitivity%s", "");
-    if (prm->t_out || prm->n_out > 0) return fail(PCK_E_ARG, "pck_drc_multi_adjoint takes no trajectory request (t_out)%s", "");
     const int64_t n = cond->n;
     rc = check_multi(net, n, obj, out);
     if (rc) return rc;
     if (n == 0) return PCK_OK;
     const hipStream_t s = (hipStream_t)stream;
-    const int NS = net->nv.NDYN, R = net->nv.NRXN;
-    StreamScratch yscr;                            // the solve's states and statuses
-    rc = salloc(yscr, sizeof(double) * (size_t)NS * n + sizeof(int32_t) * (size_t)n, s);
+    SteadyStates ss;
+    rc = solve_steady(net, cond, prm, nsteps, s, ss);
     if (rc) return rc;
-    double* y = yscr.as<double>();
-    int32_t* st = (int32_t*)(y + (int64_t)NS * n);
-    pck_solve_params p = *prm;
-    p.want_activity = 0;
-    SolveArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y = y; a.ld_y = n; a.tof = nullptr; a.status = st; a.nsteps = nsteps;
-    a.G = 1;
-    StreamScratch kscr;                            // kf | kr, [R][n] each (launch_solve)
-    rc = launch_solve(net, cond, &p, a, s, kscr);
-    if (rc) return rc;
-    const double* kf = kscr.as<double>();
-    const double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
-    return launch_multi_at(net, cond, kf, kr, n, y, n, st, obj, out, s);
+    return launch_multi_at(net, cond, ss.kf, ss.kr, n, ss.y, n, ss.st, obj, out, s);
 }

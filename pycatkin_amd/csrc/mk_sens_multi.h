@@ -12,13 +12,15 @@
 //     A^T lambda_m = g_m,   s_mj = wr[m][j] - sum_i lambda_mi w_i S_ij,
 //     xi[m][j] = d ln J_m / d ln k_j at fixed K_j = net_j s_mj / J_m.
 //
-// Assembly, replaced rows and equilibration are sens_body's, statement for
-// statement.  The LU differs in two points: no right-hand side is eliminated
-// along, and the multiplier l of a row at step k is kept in the entry it
-// annihilates (M[gl * G + k], dead in sens_body), so that every objective
-// replays the forward elimination on its own g_m (G multiply-subtracts per
-// step for the group, against G^2 / 2 of the factorisation) and then
-// back-substitutes as sens_body does.
+// Assembly, replaced rows, equilibration, the LU and the solve are the group
+// schedule of mk_adjoint.h, as sens_body (mk_sens.h) uses them: the LU carries
+// no right-hand side and keeps the multiplier l of a row at step k in the entry
+// it annihilates, so that every objective replays the forward elimination on
+// its own g_m (G multiply-subtracts per step for the group, against G^2 / 2 of
+// the factorisation) and then back-substitutes.  What differs from sens_body:
+// the matrix is factored before any objective is judged (val is written for
+// every condition), a non-finite entry of L or U is PCK_ST_SENS_SINGULAR, and a
+// non-finite lambda_m is PCK_ST_NONFINITE for that objective alone.
 //
 // Layout: as sens_body, G = 16 / 32 / 64 lanes per condition, lane i owns
 // species i and row i of M = A^T in LDS.  The matrix has to survive the K
@@ -67,102 +69,19 @@ __device__ __forceinline__ void multi_body(const NetView& nv, const GrpView& gv,
     const double NaN = __builtin_nan("");
 
     int st = status_in ? status_in[c] : PCK_ST_OK;
-    double yi = 0.0, sr = 1.0, dc = 1.0, wi = 0.0;
+    double sr = 1.0, dc = 1.0, wi = 0.0;
     int step = -1;
     if (st == PCK_ST_OK) {                         // group-uniform
-        for (int q = 0; q < G; ++q) M[q * G + gl] = dd_of(0.0);
-        // row gl of A into column gl of M, and the row's rate f
-        double rs = 0.0;
-        bool pv = false;
-        int law = -1;
-        dd f = dd_of(0.0);
-        if (row) {
-            const double* d = nv.dyn + 4 * gl;
-            const double T = cv.T[c * cv.sT];
-            rs = (d[2] != 0.0) ? d[1] + d[2] * T : d[1];   // reactor.py:34-41, as mk_group.h: grp_setup
-            const double fl = d[3];
-            yi = yin[gl * ld_y + c];
-            for (int e = gv.row[gl]; e < gv.row[gl + 1]; ++e) {
-                const uint4 q4 = gv.ent[e];
-                const int r = ent_r(q4), np = ent_np(q4);
-                const dd w = two_prod(rs, ent_s(q4));
-                const uint4 rec = gv.rx[r];
-                dd a, b;
-                sens_keff(nv, in, r, a, b);
-                f = dd_add(f, dd_mul(w, sens_rate(nv, in, rec, a, b, -1)));
-                for (int k = 0; k < np; ++k) {
-                    dd* m = M + ent_species(q4, k) * G + gl;
-                    *m = dd_add(*m, dd_mul(w, sens_rate(nv, in, rec, a, b, k)));
-                }
-            }
-            if (fl != 0.0) {                        // the CSTR flow term fl (in - y)
-                const double yin_i = cv.inflow ? cv.inflow[gl * cv.ld_in + c * cv.s_in] : 0.0;
-                f = dd_add(f, dd_mul(two_sum(yin_i, -yi), fl));
-                M[gl * G + gl] = dd_add(M[gl * G + gl], dd_of(-fl));
-            }
-            for (int l = 0; l < nv.NCONS; ++l)
-                if (nv.cpiv[l] == gl) { pv = true; law = l; }
-        }
-        // rows replaced as in mk_solver.h: newton -- the conservation laws in
-        // their pivot rows, a unit row for a pinned species (newton_pinned)
-        const bool pin = row && !pv && yi == 0.0 && f.hi == 0.0 && f.lo == 0.0;
-        if (pv)
-            for (int q = 0; q < NS; ++q) M[q * G + gl] = dd_of(nv.C[law * NS + q]);
-        if (pin)
-            for (int q = 0; q < NS; ++q) M[q * G + gl] = dd_of(q == gl ? 1.0 : 0.0);
-        wi = (pv || pin) ? 0.0 : rs;               // b_j's weight on this row
-        wsync();
-
-        // equilibration by powers of two (exact): the columns of M (the rows of
-        // A), then its rows; both scales are kept for the objectives
-        for (int q = 0; q < NS; ++q) {
-            const double s = inv_pow2(gmax<G>(row ? fabs(M[gl * G + q].hi) : 0.0));
-            if (row) M[gl * G + q] = dd_scale(M[gl * G + q], s);
-            if (q == gl) dc = s;
-        }
-        if (row) {
-            double m = 0.0;
-            for (int q = 0; q < NS; ++q) m = fmax(m, fabs(M[gl * G + q].hi));
-            sr = inv_pow2(m);
-            for (int q = 0; q < NS; ++q) M[gl * G + q] = dd_scale(M[gl * G + q], sr);
-        }
-
-        // LU with partial pivoting, row per lane.  Rows are not moved: `step`
-        // is the column a row was the pivot of.  The multiplier of a row stays
-        // in the entry it annihilates.
-        bool ok = true;
-        for (int k = 0; k < NS; ++k) {
-            const bool fr = row && step < 0;
-            double a = fr ? fabs(M[gl * G + k].hi) : -1.0;
-            if (a != a) a = INFINITY;              // a NaN must not hide behind fmax
-            const double m = gmax<G>(a);
-            if (!(m > 0.0) || !isfinite(m)) { ok = false; break; }    // group-uniform
-            const int p = (G - 1) - gmaxi<G>((fr && a == m) ? (G - 1) - gl : -1);     // the lowest such lane
-            if (gl == p) step = k;
-            const dd piv = M[p * G + k];
-            if (fr && gl != p) {
-                const dd l = dd_div(M[gl * G + k], piv);
-                for (int q = k + 1; q < NS; ++q) M[gl * G + q] = dd_sub(M[gl * G + q], dd_mul(l, M[p * G + q]));
-                M[gl * G + k] = l;
-            }
-            wsync();                               // the next pivot row is complete before it is read
-        }
-        // a non-finite factor anywhere in L or U
-        if (ok) {
-            double fin = 1.0;
-            if (row)
-                for (int q = 0; q < NS; ++q) fin = isfinite(M[gl * G + q].hi + M[gl * G + q].lo) ? fin : 0.0;
-            ok = gmin<G>(fin) > 0.0;
-        }
-        if (!ok) st = PCK_ST_SENS_SINGULAR;
+        double rs;
+        const bool repl = grp_assemble<G>(nv, gv, cv, in, M, gl, row, rs);
+        wi = repl ? 0.0 : rs;                      // b_j's weight on this row
+        grp_equilibrate<G>(M, NS, gl, row, dc, sr);
+        dd none = dd_of(0.0);                      // no right-hand side is carried
+        if (!(grp_factor<G, false>(M, NS, gl, row, step, none) && grp_factor_finite<G>(M, NS, gl, row)))
+            st = PCK_ST_SENS_SINGULAR;
     }
     if (gl == 0 && out.status) out.status[c] = st;
 
-    // forward / reverse side of reaction j
-    auto sides = [&](int j, dd& rf, dd& rr) {
-        sens_keff(nv, in, j, rf, rr);
-        sens_sides(nv, in, gv.rx[j], rf, rr, -1);
-    };
     for (int m = 0; m < ob.K; ++m) {
         const double* wr = ob.wr ? ob.wr + (int64_t)m * R : nullptr;
         const double* wy = ob.wy ? ob.wy + (int64_t)m * NS : nullptr;
@@ -174,7 +93,7 @@ __device__ __forceinline__ void multi_body(const NetView& nv, const GrpView& gv,
                 const double w = wr[j];
                 if (w == 0.0) continue;
                 dd rf, rr;
-                sides(j, rf, rr);
+                sens_fr(nv, gv, in, j, rf, rr);
                 jp = dd_add(jp, dd_mul(dd_sub(rf, rr), w));
             }
         if (wy && row) jp = dd_add(jp, two_prod(wy[gl], yin[gl * ld_y + c]));
@@ -193,38 +112,13 @@ __device__ __forceinline__ void multi_body(const NetView& nv, const GrpView& gv,
         dd g = dd_of(0.0);
         if (row) {
             if (wr)
-                for (int j = 0; j < R; ++j) {
-                    const double w = wr[j];
-                    if (w == 0.0) continue;
-                    const uint4 rec = gv.rx[j];
-                    const int np = rx_np(rec);
-                    for (int k = 0; k < np; ++k) {
-                        if ((rx_field(rec, k) & 63) != gl) continue;
-                        dd a, b;
-                        sens_keff(nv, in, j, a, b);
-                        g = dd_add(g, dd_mul(sens_rate(nv, in, rec, a, b, k), w));
-                    }
-                }
+                for (int j = 0; j < R; ++j)
+                    if (wr[j] != 0.0) grp_g_add<true>(nv, gv, in, j, wr[j], gl, g);
             if (wy) g = dd_add(g, dd_of(wy[gl]));
             g = dd_scale(g, sr);
         }
-        // the forward elimination replayed from the stored multipliers: at step
-        // k every row still free then, the pivot apart, subtracts l g_pivot
-        for (int k = 0; k < NS; ++k) {
-            const int p = gmaxi<G>((row && step == k) ? gl : -1);
-            const dd gp = gbcast_dd<G>(g, p);
-            if (row && step > k) g = dd_sub(g, dd_mul(M[gl * G + k], gp));
-        }
-        // back substitution: lane k keeps lambda_k
-        dd lam = dd_of(0.0);
-        for (int k = NS - 1; k >= 0; --k) {
-            const int p = gmaxi<G>((row && step == k) ? gl : -1);
-            const dd x = dd_div(gbcast_dd<G>(g, p), M[p * G + k]);
-            if (gl == k) lam = x;
-            if (row && step < k) g = dd_sub(g, dd_mul(M[gl * G + k], x));
-        }
-        const double lsum = lam.hi + lam.lo;
-        if (!(gmin<G>((!row || isfinite(lsum)) ? 1.0 : 0.0) > 0.0)) {     // group-uniform: an overflow of this objective alone
+        const dd lam = grp_solve<G, false>(M, NS, gl, row, step, g);
+        if (!grp_finite<G>(lam, row)) {            // group-uniform: an overflow of this objective alone
             for (int j = gl; j < R; j += G) xi[j * out.ld_xi] = NaN;
             if (gl == 0 && out.ostatus) out.ostatus[m * out.ld_os + c] = PCK_ST_NONFINITE;
             continue;
@@ -236,12 +130,8 @@ __device__ __forceinline__ void multi_body(const NetView& nv, const GrpView& gv,
         // xi[m][j] = net_j s_mj / J_m, lane per reaction
         for (int j = gl; j < R; j += G) {
             dd rf, rr;
-            sides(j, rf, rr);
-            dd s = dd_of(wr ? wr[j] : 0.0);
-            for (int i = 0; i < NS; ++i) {
-                const double sv = nv.S[i * R + j];
-                if (sv != 0.0) s = dd_sub(s, dd_mul(Lw[i], sv));
-            }
+            sens_fr(nv, gv, in, j, rf, rr);
+            const dd s = adj_bracket(nv, j, wr ? wr[j] : 0.0, [&](int i) { return Lw[i]; });
             const dd x = dd_div(dd_mul(dd_sub(rf, rr), s), J);
             xi[j * out.ld_xi] = x.hi + x.lo;
         }

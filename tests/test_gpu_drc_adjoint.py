@@ -1,4 +1,5 @@
-"""The analytic degree of rate control on the device (csrc/mk_sens.h:
+"""The analytic degree of rate control on the device (csrc/mk_sens.h over
+csrc/mk_adjoint.h:
 k_drc_adjoint; pck_drc_at, pck_drc_adjoint; System.drc_at,
 System.drc_batch(method='analytic')) against tests/golden/
 drc_adjoint_fixture.npz (make_drc_adjoint_fixture.py: the adjoint formula of

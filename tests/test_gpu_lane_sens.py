@@ -146,8 +146,8 @@ def test_drc_at_lane_is_sensitivity_at_lane_bitwise(P, inputs, tag):
 
 
 # ------------------------------------------------------------------ 4. divergence inside a wavefront
-def interleaved(P, inputs, cases, n, status_in=None, k_zero_but=None):
-    """sensitivity_at(adjoint_kernel='lane') of n conditions, condition q the
+def interleaved(P, inputs, cases, n, status_in=None, k_zero_but=None, kernel='lane'):
+    """sensitivity_at(adjoint_kernel=kernel) of n conditions, condition q the
     case cases[q % len(cases)]: its own state, rate constants and descriptors.
     k_zero_but = {position in `cases`: reaction}: that case's rate constants
     all 0 but the named reaction's, and its O* coverage set to its CO* one."""
@@ -171,8 +171,8 @@ def interleaved(P, inputs, cases, n, status_in=None, k_zero_but=None):
     a = np.repeat(SG.scase(VOLCANO_ALL[0])['dir_a'][rows][None, :, None], n, axis=2)
     cc = np.repeat(SG.scase(VOLCANO_ALL[0])['dir_c'][rows][None, :, None], n, axis=2)
     out = s.sensitivity_at(tof_terms, Y, k=(kf, kr), T=np.full(n, float(c0['T'])), p=np.full(n, float(c0['p'])),
-                           desc=desc, status_in=status_in, directions=(a, cc), adjoint_kernel='lane')
-    assert s.device(tof_terms).sens_lanes() == 1
+                           desc=desc, status_in=status_in, directions=(a, cc), adjoint_kernel=kernel)
+    assert s.device(tof_terms).sens_lanes() == (1 if kernel == 'lane' else 16)
     flat = {key: np.array([out[key][x] for x in plan.reactions]) for key in ('xi', 'sf', 'sr')}
     flat['order'] = np.array([out['order'][x] for x in plan.fix]).reshape(len(plan.fix), n)
     for key in ('dir', 'tof0', 'status', 'err'):
@@ -183,31 +183,26 @@ def interleaved(P, inputs, cases, n, status_in=None, k_zero_but=None):
 _ONE = {}
 
 
-def volcano_singles(P, inputs, k_zero_but=None):
-    """The n = 1 answer of each of the six volcano cases."""
-    key = tuple(sorted((k_zero_but or {}).items()))
+def volcano_singles(P, inputs, k_zero_but=None, kernel='lane'):
+    """The n = 1 answer of each of the six volcano cases, by the named kernel."""
+    key = (kernel,) + tuple(sorted((k_zero_but or {}).items()))
     if key not in _ONE:
         cases = [D.case(i) for i in VOLCANO_ALL]
         _ONE[key] = cases, [interleaved(P, inputs, [c], 1, k_zero_but={0: k_zero_but[pos]} if pos in (k_zero_but or {})
-                                        else None) for pos, c in enumerate(cases)]
+                                        else None, kernel=kernel) for pos, c in enumerate(cases)]
     return _ONE[key]
 
 
 FLAT_KEYS = ('xi', 'sf', 'sr', 'order', 'dir', 'tof0', 'err')
 
 
-@pytest.mark.parametrize('n', [3, 63, 64, 65, 129])
-def test_lanes_of_a_wavefront_diverge(P, inputs, n):
-    """All six volcano cases interleaved in one call (different pivot orders,
-    the flagged case among them), status_in 4 on every fifth lane: every lane
-    is bitwise its own n = 1 answer; a gated lane has NaN outputs, a tof0 and
-    keeps its 4."""
-    cases, one = volcano_singles(P, inputs)
+def check_conditions_diverge(P, inputs, n, kernel):
+    cases, one = volcano_singles(P, inputs, kernel=kernel)
     assert len(cases) == 6 and SG.FLAGGED[0] in VOLCANO_ALL
     sts = [int(o['status'][0]) for o in one]
     assert ST_SENS_PRECISION in sts and 0 in sts
     si = np.array([4 if q % 5 == 2 else 0 for q in range(n)], np.int32)
-    r = interleaved(P, inputs, cases, n, status_in=si)
+    r = interleaved(P, inputs, cases, n, status_in=si, kernel=kernel)
     for q in range(n):
         ref = one[q % 6]
         if si[q]:
@@ -220,6 +215,29 @@ def test_lanes_of_a_wavefront_diverge(P, inputs, n):
                 np.testing.assert_array_equal(r[key][..., q], ref[key][..., 0], err_msg='%s lane %d' % (key, q))
 
 
+def check_singular_beside_regular(P, inputs, n, kernel):
+    zero = {1: 'CO_ox'}
+    cases, one = volcano_singles(P, inputs, zero, kernel=kernel)
+    assert one[1]['status'][0] == ST_SENS_SINGULAR and np.isfinite(one[1]['tof0'][0]) and one[1]['tof0'][0] != 0.0
+    assert np.all(np.isnan(one[1]['xi'])) and np.all(np.isnan(one[1]['dir']))
+    r = interleaved(P, inputs, cases, n, k_zero_but=zero, kernel=kernel)
+    for q in range(n):
+        ref = one[q % 6]
+        assert r['status'][q] == ref['status'][0], q
+        for key in FLAT_KEYS:
+            np.testing.assert_array_equal(r[key][..., q], ref[key][..., 0], err_msg='%s lane %d' % (key, q))
+    assert np.count_nonzero(r['status'] == ST_SENS_SINGULAR) == len([q for q in range(n) if q % 6 == 1])
+
+
+@pytest.mark.parametrize('n', [3, 63, 64, 65, 129])
+def test_lanes_of_a_wavefront_diverge(P, inputs, n):
+    """All six volcano cases interleaved in one call (different pivot orders,
+    the flagged case among them), status_in 4 on every fifth lane: every lane
+    is bitwise its own n = 1 answer; a gated lane has NaN outputs, a tof0 and
+    keeps its 4."""
+    check_conditions_diverge(P, inputs, n, 'lane')
+
+
 @pytest.mark.parametrize('n', [3, 65])
 def test_singular_lane_beside_regular_ones(P, inputs, n):
     """One case with every rate constant but CO_ox's zeroed and equal CO* and O*
@@ -228,17 +246,31 @@ def test_singular_lane_beside_regular_ones(P, inputs, n):
     meets an exactly zero pivot -> status 7 (PCK_ST_SENS_SINGULAR, a handled
     status) and NaN on that lane alone; its neighbours are bitwise their n = 1
     answers."""
-    zero = {1: 'CO_ox'}
-    cases, one = volcano_singles(P, inputs, zero)
-    assert one[1]['status'][0] == ST_SENS_SINGULAR and np.isfinite(one[1]['tof0'][0]) and one[1]['tof0'][0] != 0.0
-    assert np.all(np.isnan(one[1]['xi'])) and np.all(np.isnan(one[1]['dir']))
-    r = interleaved(P, inputs, cases, n, k_zero_but=zero)
-    for q in range(n):
-        ref = one[q % 6]
-        assert r['status'][q] == ref['status'][0], q
-        for key in FLAT_KEYS:
-            np.testing.assert_array_equal(r[key][..., q], ref[key][..., 0], err_msg='%s lane %d' % (key, q))
-    assert np.count_nonzero(r['status'] == ST_SENS_SINGULAR) == len([q for q in range(n) if q % 6 == 1])
+    check_singular_beside_regular(P, inputs, n, 'lane')
+
+
+# The same two with adjoint_kernel='group' (csrc/mk_sens.h: k_sens_adjoint<16>;
+# sens_lanes() == 16 is asserted in interleaved): the volcano has 4 species, so
+# four conditions share one wavefront and one block.  n = 3, 4, 5, 9: a partly
+# filled block, a full one, the first condition of the second and third blocks.
+GROUP_N = [3, 4, 5, 9]
+
+
+@pytest.mark.parametrize('n', GROUP_N)
+def test_groups_of_a_wavefront_diverge(P, inputs, n):
+    """As test_lanes_of_a_wavefront_diverge by the group kernel: the groups of a
+    wavefront pivot differently and leave at different exits; every condition
+    is bitwise its own n = 1 group-kernel answer, a gated one has NaN outputs,
+    a tof0 and keeps its 4."""
+    check_conditions_diverge(P, inputs, n, 'group')
+
+
+@pytest.mark.parametrize('n', GROUP_N)
+def test_singular_group_beside_regular_ones(P, inputs, n):
+    """As test_singular_lane_beside_regular_ones by the group kernel: status 7
+    and NaN on the singular condition alone, whose group leaves at the
+    factorisation while the other groups of its wavefront go on."""
+    check_singular_beside_regular(P, inputs, n, 'group')
 
 
 # ------------------------------------------------------------------ 5. beyond the one-lane limit

@@ -137,16 +137,16 @@ NETWORKS = {'l8': (('l8_0', 'l8_1'), None, None), 'volcano': (('volcano_-1_-1', 
 _KINDS = {}
 
 
-def singles(P, inputs, key):
-    """(System, the four kinds, the objectives, each kind's n = 1 answer)"""
-    if key not in _KINDS:
+def singles(P, inputs, key, kernel='lane'):
+    """(System, the four kinds, the objectives, each kind's n = 1 answer by the named kernel)"""
+    if (key, kernel) not in _KINDS:
         names, keep, equal = NETWORKS[key]
         roots = [mcase(nm) for nm in names]
         keep = str(roots[0]['c']['tof_terms'][0]) if keep is None else keep
         s, cols = kinds_of(P, inputs, roots, keep, equal)
         objs = DM.objectives_of(roots[0])
-        _KINDS[key] = s, cols, objs, [run_cols(s, [c], objs) for c in cols]
-    return _KINDS[key]
+        _KINDS[key, kernel] = s, cols, objs, [run_cols(s, [c], objs, kernel) for c in cols]
+    return _KINDS[key, kernel]
 
 
 @pytest.mark.parametrize('key', ['l8', 'volcano'])
@@ -168,14 +168,9 @@ def test_the_four_kinds_alone(P, inputs, key):
     np.testing.assert_array_equal(one[3]['val'], one[1]['val'])
 
 
-@pytest.mark.parametrize('n', [1, 63, 64, 65, 130])
-@pytest.mark.parametrize('key', ['l8', 'volcano'])
-def test_lanes_of_a_wavefront_diverge(P, inputs, key, n):
-    """The four kinds interleaved in one call (different pivot orders, a lane
-    that leaves at the factorisation, a gated one): every condition's val, xi,
-    status and ostatus are bitwise its own n = 1 answer."""
-    s, cols, objs, one = singles(P, inputs, key)
-    r = run_cols(s, [cols[q % 4] for q in range(n)], objs)
+def check_conditions_diverge(P, inputs, key, n, kernel):
+    s, cols, objs, one = singles(P, inputs, key, kernel)
+    r = run_cols(s, [cols[q % 4] for q in range(n)], objs, kernel)
     for q in range(n):
         ref = one[q % 4]
         assert r['status'][q] == ref['status'][0], q
@@ -184,6 +179,27 @@ def test_lanes_of_a_wavefront_diverge(P, inputs, key, n):
     if n >= 4:
         assert np.count_nonzero(r['status'] == ST_SENS_SINGULAR) == len([q for q in range(n) if q % 4 == 2])
         assert np.count_nonzero(r['status'] == ST_NEWTON) == len([q for q in range(n) if q % 4 == 3])
+
+
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 130])
+@pytest.mark.parametrize('key', ['l8', 'volcano'])
+def test_lanes_of_a_wavefront_diverge(P, inputs, key, n):
+    """The four kinds interleaved in one call (different pivot orders, a lane
+    that leaves at the factorisation, a gated one): every condition's val, xi,
+    status and ostatus are bitwise its own n = 1 answer."""
+    check_conditions_diverge(P, inputs, key, n, 'lane')
+
+
+@pytest.mark.parametrize('n', [3, 4, 5, 9])
+@pytest.mark.parametrize('key', ['l8', 'volcano'])
+def test_groups_of_a_wavefront_diverge(P, inputs, key, n):
+    """The same by the group kernel (csrc/mk_sens_multi.h: k_multi_adjoint<16>, 16
+    lanes per condition as run_cols asserts, four conditions to a wavefront and
+    a block): a partly filled block, a full one, the first condition of the
+    second and third blocks.  The singular condition's group goes through the
+    objective loop with status 7 beside groups that solve; every condition is
+    bitwise its own n = 1 group-kernel answer."""
+    check_conditions_diverge(P, inputs, key, n, 'group')
 
 
 # ------------------------------------------------------------------ 3. objectives are independent

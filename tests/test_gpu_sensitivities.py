@@ -1,4 +1,5 @@
-"""The adjoint sensitivities on the device (csrc/mk_sens.h: k_sens_adjoint;
+"""The adjoint sensitivities on the device (csrc/mk_sens.h: k_sens_adjoint, its
+steps and output tail in csrc/mk_adjoint.h;
 pck_sens_at, pck_sens_adjoint; System.sensitivity_at / sensitivity_batch)
 against tests/golden/sensitivity_fixture.npz (make_sensitivity_fixture.py: the
 formulas of tests/_sens_ext.py at 400 bits, at the states and rate constants of

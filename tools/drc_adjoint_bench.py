@@ -1,5 +1,5 @@
-"""Time the analytic degree of rate control (pck_drc_adjoint, csrc/mk_sens.h)
-against the finite-difference one (pck_drc) and against its own pieces.
+"""Time the analytic degree of rate control (pck_drc_adjoint, csrc/mk_sens.h;
+its steps in csrc/mk_adjoint.h) against the finite-difference one (pck_drc) and against its own pieces.
 
   dmtm      the bench's 64 x 64 grid of T 400-800 K x p 1e4-1e6 Pa, TOF = r5 + r9,
             steady solves (System.drc_batch(steady=True)'s settings)

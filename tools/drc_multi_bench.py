@@ -1,5 +1,6 @@
 """Time the multi-objective analytic degree of rate control (pck_drc_multi_at,
-csrc/mk_sens_multi.h: k_multi_adjoint) against the single-objective kernel of
+csrc/mk_sens_multi.h: k_multi_adjoint; the steps both group kernels share are in
+csrc/mk_adjoint.h) against the single-objective kernel of
 the same tree (pck_drc_at, csrc/mk_sens.h: k_drc_adjoint), interleaved in one
 process.
 

@@ -7,7 +7,7 @@ Workloads as tools/drc_adjoint_bench.py: dmtm (64 x 64 grid), syn24 (4 096
 conditions), volcano (1024 x 1024 grid); cstr (the Pd111 CSTR, a sweep of 10 000
 temperatures 423 .. 623 K; its Eapp is refused -- the row scale depends on T -- so
 its direction is the fixed a = c = 1).  --adjoint-kernel group | lane picks the
-adjoint kernels (csrc/mk_sens.h / csrc/mk_sens_lane.h; lane: networks of at
+adjoint kernels (csrc/mk_sens.h over csrc/mk_adjoint.h / csrc/mk_sens_lane.h; lane: networks of at
 most 8 dynamic species).  Per workload, on the current stream:
   solve       pck_solve alone (System.sensitivity_batch's settings)
   drc_at      pck_drc_at at the solve's states: k_drc_adjoint alone
