@@ -39,6 +39,9 @@
  *                          Energy.evaluate_energy_span_model  energy.py:238
  *   pck_ensemble_noise  <- Uncertainty.get_correlated_state_noises pycatkin/classes/uncertainty.py:35
  *   pck_ensemble_stats  <- Uncertainty.get_mean_property_value uncertainty.py:115 (np.mean / np.std over runs)
+ *   pck_eigvals         <- the np.linalg.eigvals of SteadyStateSolver.test_convergence
+ *   pck_stability_at       pycatkin/classes/solver.py:102-106 and of solve_ode solver.py:156-158
+ *   pck_stability          (Jacobian and eigenvalues on the device; + the reduced Jacobian)
  *
  * All functions return 0 on success and a negative PCK_E_* code on failure;
  * pck_last_error() returns a message for the calling thread.  Device pointers
@@ -233,6 +236,9 @@ typedef struct {
  * double-double no longer resolves the per-direction sensitivities (err > err_max):
  * sf, sr, order, order_in and dir are NaN; xi and tof0 are written and reliable */
 #define PCK_ST_SENS_PRECISION 8
+/* pck_eigvals / pck_stability_at / pck_stability: the QR iteration spent its
+ * 30 * max(10, ns) sweeps without isolating every eigenvalue; outputs are NaN */
+#define PCK_ST_EIG_NOCONV 9
 
 int pck_abi_version(void);
 const char* pck_last_error(void);
@@ -596,6 +602,67 @@ typedef struct {
  * ld_v < n_rep*block, ld_out < n_rep. */
 int pck_ensemble_stats(const double* v, int64_t ld_v, int64_t n_rows, const int32_t* status, uint32_t ok_mask,
                        int64_t n_rep, int64_t block, int64_t skip, const pck_ens_stats* out, void* stream);
+
+/* ---- linear stability: eigenvalues of steady Jacobians --------------------------
+ * Outputs of pck_eigvals / pck_stability_at / pck_stability (device pointers, each
+ * optional), per condition.  A condition whose status is not PCK_ST_OK gets NaN in
+ * every double and -1 in n_pos. */
+typedef struct {
+    double* wr; double* wi; int64_t ld_w;   /* [ns_eff][ld_w] real / imaginary parts; a conjugate pair is
+                                             *   adjacent, positive imaginary part first; the order is
+                                             *   otherwise unspecified */
+    double* re_max;              /* [n] spectral abscissa: the largest real part */
+    double* im_max;              /* [n] |Im| of that eigenvalue (the largest among equal real parts) */
+    double* re_min;              /* [n] the most negative real part */
+    double* scale;               /* [n] ns_eff * eps * ||B||_F, B the scale-balanced matrix: the size of
+                                  *   fp64 rounding in the eigenvalues (the backward error of Hessenberg QR
+                                  *   on B), not a bound for ill-conditioned ones.  An eigenvalue smaller
+                                  *   than scale is not resolved: its sign means nothing */
+    int32_t* n_pos;              /* [n] eigenvalues with real part > re_tol */
+    int32_t* status;             /* [n] PCK_ST_* */
+} pck_eig_out;
+
+/* Eigenvalues of n real ns x ns matrices in the layout pck_jacobian writes (entry
+ * (i, k) of condition c at a[(i*ns + k)*ld + c]; never modified), fp64: balancing by
+ * powers of two (scaling only), Householder reduction to Hessenberg form, Francis
+ * double-shift QR (csrc/mk_eig.h).  Network-free.  Replaces the np.linalg.eigvals of
+ * SteadyStateSolver.test_convergence (pycatkin/classes/solver.py:102-106) and of
+ * solve_ode (solver.py:156-158) for a batch.
+ * lanes: PCK_SENS_LANES_ONE (one lane per condition, ns <= PCK_MAX_DYN_LANE, else
+ * PCK_E_SIZE), PCK_SENS_LANES_GROUP (16 / 32 / 64 lanes per condition),
+ * PCK_SENS_LANES_AUTO (one lane up to PCK_MAX_DYN_LANE, else groups).  lanes_used
+ * (optional, host): 1, 16, 32 or 64.  The result for a matrix does not depend on the
+ * rest of the batch, bit for bit.
+ * status_in (optional) gates the conditions as in pck_drc_at: a row that is not
+ * PCK_ST_OK keeps its status.  PCK_ST_NONFINITE: a non-finite entry (or eigenvalue);
+ * PCK_ST_EIG_NOCONV: the sweep budget is spent.
+ * PCK_E_ARG: ns < 1, ld (or ld_w with wr / wi) below n, NULL a / out, an unknown
+ * mode; PCK_E_SIZE: ns > PCK_MAX_DYN.  n = 0 is a no-op. */
+int pck_eigvals(const double* a, int ns, int64_t n, int64_t ld, const int32_t* status_in, double re_tol,
+                int lanes, const pck_eig_out* out, int32_t* lanes_used, void* stream);
+
+/* Linear stability at given states y ([NS][ld_y]), kf / kr as pck_rate_constants
+ * gives them: pck_jacobian into stream-ordered scratch, then the kernel of
+ * pck_eigvals -- the Jacobian never leaves the device (solver.py:102-106, :156-158
+ * copy it to the host for np.linalg.eigvals).
+ * reduce = 0: the full Jacobian, ns_eff = NS (the reference's test; with a
+ * conservation law it has a structurally zero eigenvalue that fp64 returns as
+ * +- scale).  reduce = 1: the Jacobian restricted to the conservation class,
+ * ns_eff = NS - NCONS: with the laws C in reduced row-echelon form and pivots p_l,
+ *   Jr[i][q] = J[i][q] - sum_l J[i][p_l] C[l][q] / C[l][p_l]   (i, q not pivots),
+ * whose spectrum has no structural zero (NCONS = 0: the same matrix).
+ * PCK_E_ARG also for reduce outside 0 / 1, NS - NCONS < 1, bad kf / kr / y. */
+int pck_stability_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                     int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in, int reduce,
+                     double re_tol, int lanes, const pck_eig_out* out, int32_t* lanes_used, void* stream);
+
+/* One steady solve (pck_solve with prm->newton = 1, as pck_drc_adjoint) and then
+ * pck_stability_at at its states, with the solve's own rate constants.  nsteps
+ * (optional): the solve's steps.  A condition without a reached root keeps that
+ * status and gets NaN outputs.  PCK_E_ARG: prm->newton == 0, a trajectory request. */
+int pck_stability(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm, int reduce,
+                  double re_tol, int lanes, const pck_eig_out* out, int32_t* lanes_used, int32_t* nsteps,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_netw
             'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
             'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint', 'pck_sens_at', 'pck_sens_adjoint',
             'pck_network_set_sens_lanes', 'pck_network_sens_lanes', 'pck_drc_multi_at', 'pck_drc_multi_adjoint',
-            'pck_network_set_multi_lanes')
+            'pck_network_set_multi_lanes', 'pck_eigvals', 'pck_stability_at', 'pck_stability')
 
 ABI_VERSION = 10
 
@@ -42,6 +42,11 @@ SENS_LANES_MODES = {'group': SENS_LANES_GROUP, 'lane': SENS_LANES_ONE, 'auto': S
 ST_OK, ST_MAXSTEPS, ST_STEPFAIL, ST_NONFINITE, ST_NEWTON, ST_NEWTON_LOOSE, ST_DRC_MIXED = range(7)
 ST_SENS_SINGULAR = 7
 ST_SENS_PRECISION = 8
+ST_EIG_NOCONV = 9
+# eig_kernel= of the stability calls -> the `lanes` argument of pck_eigvals / pck_stability_at / pck_stability
+# the per-condition outputs of pck_eig_out beside the spectrum wr / wi
+EIG_OUTPUTS = ('re_max', 'im_max', 're_min', 'scale', 'n_pos', 'status')
+EIG_LANES_MODES = {'group': SENS_LANES_GROUP, 'lane': SENS_LANES_ONE, 'auto': SENS_LANES_AUTO}
 E_ARG, E_HIP, E_SIZE = -1, -2, -3
 
 
@@ -104,6 +109,12 @@ class MultiOut(C.Structure):
                 ('status', C.c_void_p), ('ostatus', C.c_void_p), ('ld_os', C.c_int64)]
 
 
+class EigOut(C.Structure):
+    _fields_ = [('wr', C.c_void_p), ('wi', C.c_void_p), ('ld_w', C.c_int64), ('re_max', C.c_void_p),
+                ('im_max', C.c_void_p), ('re_min', C.c_void_p), ('scale', C.c_void_p), ('n_pos', C.c_void_p),
+                ('status', C.c_void_p)]
+
+
 _lib = None
 
 
@@ -151,6 +162,11 @@ def load():
                                      C.POINTER(MultiOut), vp]
     lib.pck_drc_multi_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(MultiObj),
                                           C.POINTER(MultiOut), vp, vp]
+    lib.pck_eigvals.argtypes = [vp, C.c_int, i64, i64, vp, C.c_double, C.c_int, C.POINTER(EigOut), i32p, vp]
+    lib.pck_stability_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, C.c_int,
+                                     C.POINTER(EigOut), i32p, vp]
+    lib.pck_stability.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.c_int, C.c_double, C.c_int,
+                                  C.POINTER(EigOut), i32p, vp, vp]
     lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
     lib.pck_ensemble_noise.argtypes = [C.c_uint64, C.c_uint64, i64, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, vp]
     lib.pck_ensemble_stats.argtypes = [vp, i64, i64, vp, C.c_uint32, i64, i64, i64, C.POINTER(EnsStats), vp]

@@ -30,6 +30,12 @@ import numpy as np
 from .system import SteadyStateResults, System
 
 
+def _check_eig(eig):
+    """eig = 'host' | 'device': where the eigenvalue test of the convergence check runs"""
+    if not isinstance(eig, str) or eig not in ('host', 'device'):
+        raise ValueError("eig must be 'host' or 'device', not %r" % (eig,))
+
+
 class SolScore(NamedTuple):
     """solver.py:8-15"""
     y_surf: np.ndarray
@@ -80,15 +86,22 @@ class SteadyStateSolver:
         return not any([rate_fail, spos_fail, ssum_fail, negjac_fail])
 
     def test_convergence_batch(self, Y, desc=None, T=None, rate_tol=1e-4, coverage_tol=5e-2, pos_jac_tol=1e-2,
-                               log=False, **kwargs):
+                               log=False, eig='host', **kwargs):
         """test_convergence for surface states Y [n_surface, n] (index_map
         order) in two launches (rates, Jacobians), each column at its own
         temperature / descriptor energies; the eigenvalues of the n Jacobians
-        in one batched LAPACK call."""
+        in one batched LAPACK call (eig='host', the default), or on the device
+        (eig='device': pck_stability_at on the full _jac_ss, only the largest
+        real part and the status of each column return to the host; a column
+        whose state or Jacobian is not finite counts as failed instead of
+        raising)."""
+        _check_eig(eig)
         Y = np.asarray(Y, float)
         n = Y.shape[1]
         if n == 0:
             return np.zeros(0, bool)
+        if eig == 'device':
+            return self._test_convergence_device(Y, desc, T, rate_tol, coverage_tol, pos_jac_tol, log)
         f = self.sys._fun_ss_batch(Y, desc=desc, T=T)
         J = self.sys._jac_ss_batch(Y, desc=desc, T=T)
         rate_fail = np.max(np.abs(f), axis=0) > rate_tol
@@ -104,6 +117,25 @@ class SteadyStateSolver:
                       '        - rate_residual = %s\n        - jacobian_eigV_max = %s'
                       % (not rate_fail[c], not ssum_fail[c], not negjac_fail[c], [float(v) for v in surf_sum[:, c]],
                          float(np.max(np.abs(f[:, c]))), float(np.max(eig[c].real))))
+        return ~(rate_fail | spos_fail | ssum_fail | negjac_fail)
+
+    def _test_convergence_device(self, Y, desc, T, rate_tol, coverage_tol, pos_jac_tol, log):
+        """test_convergence_batch with the eigenvalue test on the device"""
+        n = Y.shape[1]
+        f = self.sys._fun_ss_batch(Y, desc=desc, T=T)
+        re_max, st = self.sys._jac_ss_re_max_batch(Y, desc=desc, T=T)
+        rate_fail = np.max(np.abs(f), axis=0) > rate_tol
+        spos_fail = np.any(np.round(Y, 2) < 0, axis=0)
+        y_all = np.concatenate((np.repeat(self.ygas[:, None], n, axis=1), Y))
+        surf_sum = np.array([y_all[sorted(idx)].sum(axis=0) for idx in self.sys.coverage_map.values()])
+        ssum_fail = np.any(np.abs(surf_sum - 1) > coverage_tol, axis=0)
+        negjac_fail = (st != 0) | ~(re_max <= pos_jac_tol)
+        if log:
+            for c in range(n):
+                print('    - CHECKS: rate %s | surf_sum %s | jac_eigV %s\n        - surf_sum = %s\n'
+                      '        - rate_residual = %s\n        - jacobian_eigV_max = %s'
+                      % (not rate_fail[c], not ssum_fail[c], not negjac_fail[c], [float(v) for v in surf_sum[:, c]],
+                         float(np.max(np.abs(f[:, c]))), float(re_max[c])))
         return ~(rate_fail | spos_fail | ssum_fail | negjac_fail)
 
     def _norm(self, y_surf):
@@ -152,11 +184,13 @@ class SteadyStateSolver:
         Y, ok = self.solve_ode_batch(T=[self.sys.T], tmax=tmax, test_convergence_kwargs=test_convergence_kwargs)
         return SteadyStateResults(Y[:, 0], bool(ok[0]))
 
-    def solve_ode_batch(self, T=None, tmax=1e4, test_convergence_kwargs=None, max_steps=200000):
+    def solve_ode_batch(self, T=None, tmax=1e4, test_convergence_kwargs=None, max_steps=200000, eig='host'):
         """solve_ode for a batch of temperatures in one launch: (Y [n_surface, n]
         in index_map order, success [n]).  The convergence checks run at each
-        condition's own temperature."""
+        condition's own temperature; eig as in test_convergence_batch."""
+        _check_eig(eig)
         kw = dict(test_convergence_kwargs or {})
+        kw['eig'] = eig
         kw['log'] = bool(self.verbose)
         s = self.sys
         T = np.atleast_1d(np.asarray(s.T if T is None else T, float))

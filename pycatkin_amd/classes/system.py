@@ -365,6 +365,19 @@ class System:
         inv = self._from_plan(plan)
         return J[np.ix_(inv, inv)]
 
+    def _jac_ss_re_max_batch(self, Y, desc=None, T=None):
+        """(largest real part of the eigenvalues of _jac_ss, status) [n] of the
+        surface states Y [n_surface, n], Jacobian and eigenvalues on the
+        device (pck_stability_at, the full matrix: solver.py:102-106)"""
+        plan, net, ngas = self._patched_eval()
+        n = Y.shape[1]
+        T = float(self.T) if T is None else T
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, None, desc, None, None, None)
+        kf, kr = net.rate_constants(n, T, p, d)
+        r = net.stability_at(n, T, p, self._to_plan(plan, Y), kf, kr, d, fx, inflow, None, reduce=False,
+                             lanes=_L.SENS_LANES_AUTO, want=('re_max', 'status'))
+        return r['re_max'].cpu().numpy(), r['status'].cpu().numpy()
+
     def _surface_order(self):
         return [s for s in sorted(self.index_map, key=self.index_map.get) if self.index_map[s] not in self.gas_indices]
 
@@ -1022,6 +1035,97 @@ class System:
                              newton=True, root_dist=ROOT_DIST,
                              screen=(float(screen), SCREEN_MARGIN) if screen else None)
         return self._sens_dict(plan, r, n, T, eapp)
+
+    # -- linear stability (DESIGN.md "Linear stability") --------------------------------------
+    @staticmethod
+    def _eig_mode(eig_kernel):
+        """the `lanes` argument of pck_stability_at / pck_stability of
+        eig_kernel = 'group' | 'lane' | 'auto'."""
+        if not isinstance(eig_kernel, str) or eig_kernel not in _L.EIG_LANES_MODES:
+            raise ValueError("eig_kernel must be 'group', 'lane' or 'auto', not %r" % (eig_kernel,))
+        return _L.EIG_LANES_MODES[eig_kernel]
+
+    @staticmethod
+    def _stability_dict(r, spectrum):
+        out = {k: r[k].cpu().numpy() for k in _L.EIG_OUTPUTS}
+        if spectrum:
+            out['wr'], out['wi'] = r['wr'].cpu().numpy(), r['wi'].cpu().numpy()
+        if 'nsteps' in r:
+            out['nsteps'] = r['nsteps'].cpu().numpy()
+        out['lanes'] = r['lanes']
+        verdict = np.full(out['re_max'].shape, 'marginal', dtype='<U8')
+        verdict[out['re_max'] < -out['scale']] = 'stable'
+        verdict[out['re_max'] > out['scale']] = 'unstable'
+        verdict[out['status'] != 0] = ''
+        out['verdict'] = verdict
+        return out
+
+    def stability_at(self, Y, T=None, p=None, desc=None, fix=None, inflow=None, status_in=None, k=None, reduce=True,
+                     eig_kernel='auto', spectrum=False, re_tol=0.0):
+        """Linear stability of the states Y [n_dynamic, n] in plan.dyn order --
+        solve_batch's 'y' -- without a solve (pck_stability_at): the
+        eigenvalues of the Jacobian of every condition, on the device.
+        reduce: the Jacobian restricted to the conservation class (n_dynamic -
+        n_laws eigenvalues, no structural zero) instead of the full one (the
+        reference's test, solver.py:102-106).  status_in, k as in drc_at.
+        eig_kernel: 'lane' (one lane per condition, at most 8 eigenvalues),
+        'group' (16, 32 or 64 lanes) or 'auto'.
+        Returns dict(re_max, im_max, re_min, scale, n_pos (real part > re_tol),
+        status, verdict, lanes) and, with spectrum, wr / wi [ns_eff, n].
+        scale = ns_eff * eps * ||B||_F is the size of fp64 rounding in the
+        eigenvalues: verdict is 'stable' where re_max < -scale, 'unstable'
+        where re_max > scale, else 'marginal' (not resolved in fp64); '' for a
+        condition whose status is not 0 (its numbers are NaN)."""
+        mode = self._eig_mode(eig_kernel)
+        plan = self.plan((), None)
+        Y = np.asarray(Y, float)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.ndim != 2 or Y.shape[0] != len(plan.dyn):
+            raise ValueError('Y has shape %s for %d dynamic species' % (Y.shape, len(plan.dyn)))
+        n = Y.shape[1]
+        if status_in is not None and np.size(status_in) != n:
+            raise ValueError('status_in has %d entries for %d conditions' % (np.size(status_in), n))
+        if k is not None and any(tuple(np.shape(a)) != (len(plan.reactions), n) for a in k):
+            raise ValueError('k = (kf, kr) must each have shape (%d, %d)' % (len(plan.reactions), n))
+        net = self.device((), None)
+        T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
+        kf, kr = net.rate_constants(n, T, p, d) if k is None else k
+        want = _L.EIG_OUTPUTS + (('wr', 'wi') if spectrum else ())
+        r = net.stability_at(n, T, p, Y, kf, kr, d, fx, inflow, status_in, reduce=reduce, re_tol=re_tol, lanes=mode,
+                             want=want)
+        return self._stability_dict(r, spectrum)
+
+    def stability_batch(self, T=None, p=None, desc=None, steady=True, t_end=None, rtol=None, atol=None,
+                        max_steps=200000, y0=None, fix=None, inflow=None, screen='auto', reduce=True,
+                        eig_kernel='auto', spectrum=False, re_tol=0.0):
+        """One steady solve per condition (sensitivity_batch's rule and
+        options) and stability_at at its states (pck_stability).  Returns
+        stability_at's dict plus 'nsteps'.  A condition whose solve did not
+        report a reached root keeps that status and gets NaN."""
+        if not steady:
+            raise ValueError('stability_batch needs steady=True: linear stability is that of a steady state')
+        mode = self._eig_mode(eig_kernel)
+        plan = self.plan((), None)
+        net = self.device((), None)
+        n = self._n(T, p, *(desc.values() if desc else []))
+        for a in (y0, fix, inflow):
+            if a is not None and np.ndim(a) == 2:
+                n = max(n, np.shape(a)[1])
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)
+        times = self.params['times'] or [0.0, 1.0e4]
+        rtol = STEADY_TRANSIENT[0] if rtol is None else rtol
+        atol = STEADY_TRANSIENT[1] if atol is None else atol
+        if isinstance(screen, str):
+            if screen != 'auto':
+                raise ValueError("screen must be 'auto', None or an rtol")
+            screen = SCREEN_RTOL if net.NDYN <= SCREEN_MAX_LANE_SPECIES else None
+        want = _L.EIG_OUTPUTS + (('wr', 'wi') if spectrum else ())
+        r = net.stability(n, T, p, y0, d, fx, inflow, reduce=reduce, re_tol=re_tol, lanes=mode, want=want,
+                          t0=times[0], t_end=times[-1] if t_end is None else t_end, rtol=rtol, atol=atol,
+                          max_steps=max_steps, newton=True, root_dist=ROOT_DIST,
+                          screen=(float(screen), SCREEN_MARGIN) if screen else None)
+        return self._stability_dict(r, spectrum)
 
     # -- descriptor sensitivities (DESIGN.md "One-lane adjoint") ----------------------------
     @staticmethod

@@ -1784,3 +1784,84 @@ extern "C" int pck_drc_multi_adjoint(const pck_network* net, const pck_condition
     if (rc) return rc;
     return launch_multi_at(net, cond, ss.kf, ss.kr, n, ss.y, n, ss.st, obj, out, s);
 }
+
+// ----------------------------------------------------------------------------
+// linear stability (csrc/mk_eig.h; kernels and launchers in tu_eig.hip)
+// ----------------------------------------------------------------------------
+namespace pck {
+int launch_eig(const double* a, int ns, int64_t n, int64_t ld, const int32_t* status_in, double re_tol, int lanes,
+               const pck_eig_out* out, int32_t* lanes_used, hipStream_t s);
+int launch_eig_reduce(const double* C, const int32_t* cpiv, int NS, int NCONS, const double* jac, int64_t ld,
+                      int64_t n, double* jr, hipStream_t s);
+}  // namespace pck
+
+// what pck_stability_at and pck_stability refuse before any launch
+static int check_stability(const pck_network* net, int reduce, int lanes, const pck_eig_out* out, int64_t n) {
+    if (!out) return fail(PCK_E_ARG, "stability: no outputs%s", "");
+    if (reduce != 0 && reduce != 1) return fail(PCK_E_ARG, "stability: reduce must be 0 or 1%s", "");
+    if (lanes != PCK_SENS_LANES_GROUP && lanes != PCK_SENS_LANES_ONE && lanes != PCK_SENS_LANES_AUTO)
+        return fail(PCK_E_ARG, "stability: unknown lanes mode%s", "");
+    const int NS = net->nv.NDYN;
+    if (NS < 1 || NS > PCK_MAX_DYN) return fail(PCK_E_SIZE, "stability: 1..%s%lld dynamic species", "", PCK_MAX_DYN);
+    if (reduce && NS - net->nv.NCONS < 1) return fail(PCK_E_ARG, "stability: no species left beside the conservation laws%s", "");
+    if ((out->wr || out->wi) && out->ld_w < n) return fail(PCK_E_ARG, "stability: ld_w is below n%s", "");
+    return PCK_OK;
+}
+
+// pck_jacobian into scratch, the restriction to the conservation class (reduce), the eigenvalue kernel
+static int launch_stability_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                               int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in, int reduce,
+                               double re_tol, int lanes, const pck_eig_out* out, int32_t* lanes_used, hipStream_t s) {
+    const int64_t n = cond->n;
+    const int NS = net->nv.NDYN, NC = reduce ? net->nv.NCONS : 0, nr = NS - NC;
+    StreamScratch jscr;
+    int rc = salloc(jscr, sizeof(double) * ((size_t)NS * NS + (NC ? (size_t)nr * nr : 0)) * (size_t)n, s);
+    if (rc) return rc;
+    double* jac = jscr.as<double>();
+    const double* a = jac;
+    rc = pck_jacobian(net, cond, kf, kr, ld_k, y, ld_y, jac, s);
+    if (rc) return rc;
+    if (NC) {
+        double* jr = jac + (int64_t)NS * NS * n;
+        rc = launch_eig_reduce(net->nv.C, net->nv.cpiv, NS, NC, jac, n, n, jr, s);
+        if (rc) return rc;
+        a = jr;
+    }
+    return launch_eig(a, nr, n, n, status_in, re_tol, lanes, out, lanes_used, s);
+}
+
+// The eigenvalue test of SteadyStateSolver.test_convergence (solver.py:102-106) and
+// solve_ode (:156-158) at given states, Jacobian and eigenvalues on the device.
+extern "C" int pck_stability_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                                int64_t ld_k, const double* y, int64_t ld_y, const int32_t* status_in, int reduce,
+                                double re_tol, int lanes, const pck_eig_out* out, int32_t* lanes_used, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    const int64_t n = cond->n;
+    rc = check_stability(net, reduce, lanes, out, n);
+    if (rc) return rc;
+    if (n > 0 && (!kf || !kr || ld_k < n)) return fail(PCK_E_ARG, "bad kf / kr%s", "");
+    if (n > 0 && (!y || ld_y < n)) return fail(PCK_E_ARG, "bad states y%s", "");
+    if (n == 0) return PCK_OK;
+    return launch_stability_at(net, cond, kf, kr, ld_k, y, ld_y, status_in, reduce, re_tol, lanes, out, lanes_used,
+                               (hipStream_t)stream);
+}
+
+// One steady solve, then pck_stability_at at its states (pck_drc_adjoint's shape).
+extern "C" int pck_stability(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                             int reduce, double re_tol, int lanes, const pck_eig_out* out, int32_t* lanes_used,
+                             int32_t* nsteps, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    rc = check_adjoint_params(prm, "pck_stability");
+    if (rc) return rc;
+    const int64_t n = cond->n;
+    rc = check_stability(net, reduce, lanes, out, n);
+    if (rc) return rc;
+    if (n == 0) return PCK_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    SteadyStates ss;
+    rc = solve_steady(net, cond, prm, nsteps, s, ss);
+    if (rc) return rc;
+    return launch_stability_at(net, cond, ss.kf, ss.kr, n, ss.y, n, ss.st, reduce, re_tol, lanes, out, lanes_used, s);
+}

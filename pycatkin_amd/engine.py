@@ -15,6 +15,7 @@ from .constants.physical_constants import bartoPa
 
 
 _POISON = os.environ.get('PCK_DEBUG_POISON') == '1'
+EIG_OUTPUTS = L.EIG_OUTPUTS
 
 
 def _torch():
@@ -493,6 +494,101 @@ class DeviceNetwork:
         L.check(self.lib.pck_drc_multi_adjoint(self.h, C.byref(c), C.byref(prm), C.byref(ob), C.byref(o),
                                                _ptr(out['nsteps']), _stream(torch)))
         return out
+
+    def stability_at(self, n, T, p, y, kf, kr, desc=None, fixc=None, inflow=None, status_in=None, reduce=True,
+                     re_tol=0.0, lanes=L.SENS_LANES_AUTO, want=EIG_OUTPUTS):
+        """pck_stability_at: the eigenvalues of the Jacobian at the states y
+        [NDYN, n] (kf, kr [NRXN, n] as rate_constants gives them), full or
+        reduced on the conservation laws; status_in as in drc_at.  Returns the
+        outputs of `want` (device tensors) plus 'lanes'."""
+        torch = self.torch
+        c, keep = self.conditions(n, T, p, desc, fixc, None, inflow)
+        y = torch.as_tensor(y, dtype=torch.float64, device='cuda').reshape(self.NDYN, n).contiguous()
+        kf = torch.as_tensor(kf, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        kr = torch.as_tensor(kr, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        si = _status_in(torch, status_in, n)
+        ns_eff = self.NDYN - (self.NCONS if reduce else 0)
+        o, out = _eig_io(torch, ns_eff, n, want)
+        used = C.c_int32(0)
+        L.check(self.lib.pck_stability_at(self.h, C.byref(c), _ptr(kf), _ptr(kr), n, _ptr(y), n, _ptr(si),
+                                          int(bool(reduce)), float(re_tol), int(lanes), C.byref(o), C.byref(used),
+                                          _stream(torch)))
+        out['lanes'] = int(used.value)
+        return out
+
+    def stability(self, n, T, p, y0, desc=None, fixc=None, inflow=None, reduce=True, re_tol=0.0,
+                  lanes=L.SENS_LANES_AUTO, want=EIG_OUTPUTS, **kw):
+        """pck_stability: one steady solve (kw as for solve; newton=True is
+        required) and stability_at at its states.  Returns what stability_at
+        returns plus nsteps."""
+        torch = self.torch
+        c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)
+        prm = self.params(**kw)
+        ns_eff = self.NDYN - (self.NCONS if reduce else 0)
+        o, out = _eig_io(torch, ns_eff, n, want)
+        out['nsteps'] = torch.empty(n, dtype=torch.int32, device='cuda')
+        used = C.c_int32(0)
+        L.check(self.lib.pck_stability(self.h, C.byref(c), C.byref(prm), int(bool(reduce)), float(re_tol), int(lanes),
+                                       C.byref(o), C.byref(used), _ptr(out['nsteps']), _stream(torch)))
+        out['lanes'] = int(used.value)
+        return out
+
+
+def _status_in(torch, status_in, n):
+    if status_in is None:
+        return None
+    si = torch.as_tensor(status_in, dtype=torch.int32, device='cuda').reshape(-1).contiguous()
+    if si.numel() != n:
+        raise ValueError('status_in has %d entries for %d conditions' % (si.numel(), n))
+    return si
+
+
+def _eig_io(torch, ns, n, want, ld=None):
+    """(pck_eig_out, output tensors) of the eigenvalue calls; `want` names the
+    outputs ('wr' / 'wi' come together as the spectrum [ns, ld])."""
+    bad = [k for k in want if k not in EIG_OUTPUTS + ('wr', 'wi')]
+    if bad:
+        raise ValueError('unknown eigenvalue outputs %r' % (bad,))
+    ld = n if ld is None else ld
+    o, out = L.EigOut(), {}
+    for k in want:
+        if k in ('wr', 'wi'):
+            out[k] = torch.empty((ns, ld), dtype=torch.float64, device='cuda')
+            o.ld_w = ld
+        else:
+            out[k] = torch.empty(n, dtype=torch.int32 if k in ('n_pos', 'status') else torch.float64, device='cuda')
+        setattr(o, k, _ptr(out[k]).value)
+    return o, out
+
+
+def eigvals(a, n=None, status_in=None, re_tol=0.0, lanes=L.SENS_LANES_AUTO, want=EIG_OUTPUTS + ('wr', 'wi'),
+            out=None):
+    """pck_eigvals: the eigenvalues of n real ns x ns matrices a [ns, ns, ld]
+    (the layout of DeviceNetwork.jacobian; a device tensor, or anything
+    torch.as_tensor takes), the first n <= ld of them (default: all).  `out`:
+    tensors to write into instead of fresh ones (spectrum rows [ns, ld]).
+    Returns the outputs of `want` (device tensors) plus 'lanes' (1, 16, 32 or
+    64 lanes per matrix)."""
+    lib, torch = L.load(), _torch()
+    a = torch.as_tensor(a, dtype=torch.float64, device='cuda')
+    if a.dim() != 3 or a.shape[0] != a.shape[1]:
+        raise ValueError('a must be [ns, ns, n], got %s' % (tuple(a.shape),))
+    a = a.contiguous()
+    ns, ld = int(a.shape[0]), int(a.shape[2])
+    n = ld if n is None else int(n)
+    si = _status_in(torch, status_in, n)
+    if out is None:
+        o, out = _eig_io(torch, ns, n, want, ld)
+    else:
+        o, out = L.EigOut(), dict(out)
+        for k, v in out.items():
+            setattr(o, k, _ptr(v).value)
+        o.ld_w = ld
+    used = C.c_int32(0)
+    L.check(lib.pck_eigvals(_ptr(a), ns, n, ld, _ptr(si), float(re_tol), int(lanes), C.byref(o), C.byref(used),
+                            _stream(torch)))
+    out['lanes'] = int(used.value)
+    return out
 
 
 _form_cache = {}

@@ -55,15 +55,18 @@ def descriptor_grid(C_range, O_range):
 
 
 def solve_descriptor_grid(sim_system, C_range, O_range, T=None, tmax=1e4, test_convergence_kwargs=None,
-                          max_steps=200000):
+                          max_steps=200000, eig='host'):
     """{(iC, iO): SteadyStateResults(x, success)} for every grid point: what
     the reference's per-point loop of SteadyStateSolver(system).solve_ode()
     returns (solver.py:374-418: the surface transient from the normalised
     initial state to tmax at rtol 1e-10 / atol 1e-12, then test_convergence),
     as one launch over the len(C_range) x len(O_range) conditions.
     `sim_system` is not modified (a deep copy carries the descriptor forms).
-    x is the surface part in index_map order, as solve_ode returns it."""
-    from ..classes.solver import SteadyStateSolver
+    x is the surface part in index_map order, as solve_ode returns it.
+    eig: 'host' (the default) or 'device', where the eigenvalue test of the
+    convergence check runs (SteadyStateSolver.test_convergence_batch)."""
+    from ..classes.solver import SteadyStateSolver, _check_eig
+    _check_eig(eig)
     s = copy.deepcopy(sim_system)
     names = set_descriptor_energies(s)
     s.build()
@@ -79,7 +82,8 @@ def solve_descriptor_grid(sim_system, C_range, O_range, T=None, tmax=1e4, test_c
     kw = dict(test_convergence_kwargs or {})
     kw.pop('log', None)
     solver = SteadyStateSolver(s, ss_guess=Y[:, 0])
-    ok = (r['status'] == 0) & solver.test_convergence_batch(Y, desc=desc, T=T, **kw)
+    kw.pop('eig', None)
+    ok = (r['status'] == 0) & solver.test_convergence_batch(Y, desc=desc, T=T, eig=eig, **kw)
     nO = np.size(O_range)
     return {(c // nO, c % nO): SteadyStateResults(Y[:, c], bool(ok[c])) for c in range(n)}
 
