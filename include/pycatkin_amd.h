@@ -306,6 +306,44 @@ int pck_jacobian(const pck_network* net, const pck_conditions* cond,
 int pck_solve(const pck_network* net, const pck_conditions* cond,
               const pck_solve_params* prm, const pck_outputs* out, void* stream);
 
+/* Reactor cascade (tanks in series; csrc/mk_cascade.h): `cells` equal CSTR cells at
+ * the condition's temperature, marched by one lane per condition in one launch.  Cell
+ * c is solved by the rule of pck_solve with these params (prm->newton, root_dist and
+ * screen_rtol as there); its inflow on the flow rows (species with a flow rate) is the
+ * dynamic state of cell c-1 on those rows, cell 0 takes cond->inflow.  The network's
+ * flow rate and row scale are one cell's (classes/reactor.py: PFReactor).  Rate
+ * constants and fixed-species concentrations are the condition's, computed once.
+ * start: PCK_CASCADE_START_Y0, every cell's transient starts from cond->y0 (what a
+ * loop of pck_solve calls computes); PCK_CASCADE_START_UPSTREAM, from the final state
+ * of the cell before it (cell 0 from y0).
+ * A cell that ends with PCK_ST_NEWTON passes its transient end downstream.  A cell
+ * that ends with an integrator failure (PCK_ST_MAXSTEPS / _STEPFAIL / _NONFINITE)
+ * stops the condition's march: its index goes to cell_fail and every later cell of
+ * the condition gets NaN states and TOFs, that status and 0 steps.
+ * Per-cell outputs (optional, device pointers): */
+#define PCK_MAX_CELLS 4096
+#define PCK_CASCADE_START_Y0 0
+#define PCK_CASCADE_START_UPSTREAM 1
+typedef struct {
+    int32_t cells, start;
+    double* y_cells; int64_t ld_yc;          /* [cells][NS][ld_yc] or NULL */
+    double* tof_cells; int32_t* status_cells; int32_t* nsteps_cells; int64_t ld_c;  /* [cells][ld_c], each may be NULL */
+    int32_t* cell_fail;                      /* [n], -1 where no cell failed; may be NULL */
+} pck_cascade;
+/* pck_outputs: y the outlet (the state of the last solved cell, the failing one where
+ * the march stopped); tof the mean of the cell TOFs (equal catalyst area per cell; NaN
+ * where the march stopped); status the failing status if there is one, else
+ * PCK_ST_NEWTON if any cell reported it, else PCK_ST_OK; nsteps the sum over the cells;
+ * kf / kr dumped as by pck_solve.
+ * PCK_E_SIZE (checked first): a network beyond the one-lane limits (PCK_MAX_DYN_LANE
+ * species, the k_eff block in LDS) or one set to PCK_PLAN_GROUP.  PCK_E_ARG: cells
+ * outside 1..PCK_MAX_CELLS, an unknown start, t_out / traj, retry_rtol != 0,
+ * want_activity, or a network without a flow row (identical cells).  wave_order is
+ * ignored (no preview).  Plans as pck_solve: compiled-in, hipRTC (PCK_JIT=0 disables
+ * it), runtime. */
+int pck_solve_cascade(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                      const pck_cascade* cas, const pck_outputs* out, void* stream);
+
 /* Degree of rate control for every active reaction (old_system.py:490):
  * xi[j][ld_xi] = (TOF(k_j*(1+eps)) - TOF(k_j*(1-eps))) / (2 eps TOF0).
  * tof0 (optional) receives the unperturbed TOF; status (optional) the worst

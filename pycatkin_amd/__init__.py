@@ -7,7 +7,7 @@ from .energy import TSYM, Descriptor, LinearForm, clamp0  # noqa: F401
 from .classes.state import ScalingState, State  # noqa: F401
 from .classes.energy import Energy  # noqa: F401
 from .classes.reaction import Reaction, ReactionDerivedReaction, UserDefinedReaction  # noqa: F401
-from .classes.reactor import CSTReactor, InfiniteDilutionReactor, Reactor  # noqa: F401
+from .classes.reactor import CSTReactor, InfiniteDilutionReactor, PFReactor, Reactor  # noqa: F401
 from .classes.system import SteadyStateResults, System  # noqa: F401
 from .classes.solver import SolScore, SteadyStateSolver  # noqa: F401
 from .classes.uncertainty import Uncertainty  # noqa: F401

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('PCK_LIB') or os.path.join(_HERE, 'libpycatkin_amd.so'
 # symbols declared in include/pycatkin_amd.h (checked by tests/test_capi.py)
 EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_network_destroy',
             'pck_network_dims', 'pck_network_group_lanes', 'pck_network_set_plan_mode', 'pck_energies', 'pck_rate_constants', 'pck_species_rates',
-            'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
+            'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_solve_cascade', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
             'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint', 'pck_sens_at', 'pck_sens_adjoint',
             'pck_network_set_sens_lanes', 'pck_network_sens_lanes', 'pck_drc_multi_at', 'pck_drc_multi_adjoint',
             'pck_network_set_multi_lanes', 'pck_eigvals', 'pck_stability_at', 'pck_stability')
@@ -48,6 +48,10 @@ ST_EIG_NOCONV = 9
 EIG_OUTPUTS = ('re_max', 'im_max', 're_min', 'scale', 'n_pos', 'status')
 EIG_LANES_MODES = {'group': SENS_LANES_GROUP, 'lane': SENS_LANES_ONE, 'auto': SENS_LANES_AUTO}
 E_ARG, E_HIP, E_SIZE = -1, -2, -3
+MAX_CELLS = 4096
+CASCADE_START_Y0, CASCADE_START_UPSTREAM = 0, 1
+# start= of the cascade calls -> pck_cascade.start
+CASCADE_START_MODES = {'system': CASCADE_START_Y0, 'upstream': CASCADE_START_UPSTREAM}
 
 
 class Conditions(C.Structure):
@@ -72,6 +76,12 @@ class Outputs(C.Structure):
     _fields_ = [('y', C.c_void_p), ('ld_y', C.c_int64), ('tof', C.c_void_p), ('status', C.c_void_p),
                 ('nsteps', C.c_void_p), ('kf', C.c_void_p), ('kr', C.c_void_p), ('ld_k', C.c_int64),
                 ('traj', C.c_void_p), ('ld_traj', C.c_int64)]
+
+
+class Cascade(C.Structure):
+    _fields_ = [('cells', C.c_int32), ('start', C.c_int32), ('y_cells', C.c_void_p), ('ld_yc', C.c_int64),
+                ('tof_cells', C.c_void_p), ('status_cells', C.c_void_p), ('nsteps_cells', C.c_void_p),
+                ('ld_c', C.c_int64), ('cell_fail', C.c_void_p)]
 
 
 class Landscape(C.Structure):
@@ -151,6 +161,8 @@ def load():
     lib.pck_jacobian.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp]
     lib.pck_reaction_rates.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp, i64, vp]
     lib.pck_solve.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(Outputs), vp]
+    lib.pck_solve_cascade.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(Cascade),
+                                      C.POINTER(Outputs), vp]
     lib.pck_drc.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]
     lib.pck_drc_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]
     lib.pck_drc_adjoint.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), vp, i64, vp, vp, vp, vp]

@@ -63,3 +63,24 @@ class CSTReactor(Reactor):
         if is_adsorbate:
             return (1.0, 0.0, 0.0)
         return (0.0, kB * self.catalyst_area / self.volume / bartoPa, 1.0 / self.residence_time)
+
+
+class PFReactor(CSTReactor):
+    """A catalyst bed as `cells` equal CSTR cells in series (tanks in series):
+    the outlet gas of cell k is the inflow of cell k+1.  volume, catalyst_area
+    and residence_time (or flow_rate) describe the whole bed; the device
+    coefficients are one cell's.  Solved by System.solve_cascade_batch."""
+
+    def __init__(self, name='reactor', volume=None, catalyst_area=None, residence_time=None, flow_rate=None, cells=1):
+        super().__init__(name=name, volume=volume, catalyst_area=catalyst_area, residence_time=residence_time,
+                         flow_rate=flow_rate)
+        if int(cells) != cells or int(cells) < 1:
+            raise ValueError('PFReactor: cells must be an integer >= 1, not %r' % (cells,))
+        self.cells = int(cells)
+
+    def row_coefficients(self, is_adsorbate):
+        if is_adsorbate:
+            return (1.0, 0.0, 0.0)
+        # a cell has 1/cells of the bed's volume, area and residence time:
+        # A/V is the bed's, the flow rate is cells / residence_time
+        return (0.0, kB * self.catalyst_area / self.volume / bartoPa, self.cells / self.residence_time)

@@ -17,7 +17,7 @@ from ..constants.physical_constants import R, bartoPa, eVtokJ, h, kB
 from .. import _lib as _L
 from ..energy import TKEYED, LinearForm
 from .reaction import Reaction
-from .reactor import InfiniteDilutionReactor, Reactor
+from .reactor import InfiniteDilutionReactor, PFReactor, Reactor
 from .state import State
 
 
@@ -549,6 +549,7 @@ class System:
         (DESIGN.md "Round 6")."""
         if wave_order not in ('auto', 'on', 'off'):
             raise ValueError("wave_order must be 'auto', 'on' or 'off', not %r" % (wave_order,))
+        self._refuse_pfr('solve_batch')
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
         if desc is not None and not isinstance(desc, dict):
@@ -583,6 +584,108 @@ class System:
                         wave_order={'auto': 0, 'on': 1, 'off': -1}[wave_order])
         if to_numpy:
             return {k: v.cpu().numpy() for k, v in out.items()}
+        return out
+
+    def _refuse_pfr(self, what):
+        """A PFReactor's coefficients are one cell's: the single-reactor calls
+        would silently answer for one cell of the bed."""
+        if isinstance(self.reactor, PFReactor):
+            raise ValueError('%s solves a single stirred tank; a PFReactor (%d cells) is solved by '
+                             'solve_cascade_batch' % (what, self.reactor.cells))
+
+    def solve_cascade_batch(self, cells=None, T=None, p=None, desc=None, y0=None, fix=None, inflow=None,
+                            tof_terms=(), steady=True, t_end=None, rtol=None, atol=None, max_steps=200000,
+                            newton_iters=60, root_dist='auto', screen='auto', start='system', method='auto',
+                            profile=True, to_numpy=True):
+        """A catalyst bed as `cells` CSTR cells in series at each condition
+        (tanks in series, DESIGN.md "Reactor cascade"): cell c is solved as
+        solve_batch(steady=...) solves a CSTR, with the gas of cell c-1 as its
+        inflow (cell 0: `inflow`).  cells=None takes the PFReactor's count;
+        with a plain CSTReactor, cells=N is N copies of the reactor as
+        configured.  Tolerances and the screen / root_dist defaults are
+        solve_batch's.  start: 'system' (every cell's transient starts from
+        y0 -- what a loop of solve_batch(inflow=previous outlet) computes) or
+        'upstream' (from the final state of the cell before).  method:
+        'fused' (pck_solve_cascade, one launch; networks of at most 8 dynamic
+        species), 'loop' (`cells` solves with device tensors, any network),
+        'auto' (fused where available).
+        A cell that reports status 4 passes its transient end on; an
+        integrator failure (1-3) stops that condition's march: cell_fail holds
+        the cell, later cells are NaN with that status.  Returns y [NS, n]
+        (the outlet), tof [n] (mean of the cell TOFs; NaN where the march
+        stopped), status [n] (the failing status, else 4 if any cell reported
+        4, else 0), nsteps [n] (sum), cell_fail [n] (-1: none), conversion
+        {gas: 1 - y_out / inflow} for the flow species with positive inflow
+        and, with profile, y_cells [cells, NS, n], tof_cells, status_cells,
+        nsteps_cells [cells, n]."""
+        if start not in _L.CASCADE_START_MODES:
+            raise ValueError("start must be 'system' or 'upstream', not %r" % (start,))
+        if method not in ('auto', 'fused', 'loop'):
+            raise ValueError("method must be 'auto', 'fused' or 'loop', not %r" % (method,))
+        if cells is None:
+            if not isinstance(self.reactor, PFReactor):
+                raise ValueError('cells is required unless the reactor is a PFReactor')
+            cells = self.reactor.cells
+        if isinstance(cells, bool) or int(cells) != cells or not 1 <= int(cells) <= _L.MAX_CELLS:
+            raise ValueError('cells must be an integer in 1..%d, not %r' % (_L.MAX_CELLS, cells))
+        cells = int(cells)
+        if isinstance(self.reactor, PFReactor) and cells != self.reactor.cells:
+            raise ValueError('cells=%d differs from the PFReactor\'s %d (its flow rate is one cell\'s)'
+                             % (cells, self.reactor.cells))
+        plan = self.plan(tuple(tof_terms), None)
+        off = int(plan.ip[_L.I_HDR + _L.D_DYN])
+        flow = np.asarray(plan.dp[off: off + 4 * len(plan.dyn)]).reshape(len(plan.dyn), 4)[:, 3]
+        if not np.any(flow != 0.0):
+            raise ValueError('solve_cascade_batch needs a reactor with flow (CSTReactor or PFReactor)')
+        one_lane = len(plan.dyn) <= _L.MAX_DYN_LANE
+        if method == 'fused' and not one_lane:
+            raise ValueError("method='fused' runs on the one-lane solver: at most %d dynamic species (this network "
+                             "has %d); use method='loop'" % (_L.MAX_DYN_LANE, len(plan.dyn)))
+        if method == 'auto':
+            method = 'fused' if one_lane else 'loop'
+        net = self.device(tuple(tof_terms), None)
+        if desc is not None and not isinstance(desc, dict):
+            n = max(self._n(T, p), int(desc.shape[1]))
+        else:
+            n = self._n(*([T, p] + (list(desc.values()) if desc else [])))
+        for x in (y0, inflow):
+            if x is not None and np.ndim(x) == 2:
+                n = max(n, np.shape(x)[1])
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)
+        times = self.params['times'] or [0.0, 1.0e4]
+        t0 = times[0]
+        t_end = times[-1] if t_end is None else t_end
+        if steady:
+            rtol = STEADY_TRANSIENT[0] if rtol is None else rtol
+            atol = STEADY_TRANSIENT[1] if atol is None else atol
+        if isinstance(root_dist, str):
+            if root_dist != 'auto':
+                raise ValueError("root_dist must be 'auto' or a number in [0, 1)")
+            root_dist = ROOT_DIST if (steady and t_end > t0) else 0.0
+        if isinstance(screen, str):
+            if screen != 'auto':
+                raise ValueError("screen must be 'auto', None or an rtol")
+            screen = SCREEN_RTOL if (steady and root_dist > 0.0 and net.NDYN <= SCREEN_MAX_LANE_SPECIES) else None
+        out = net.solve_cascade(n, T, p, y0, cells, d, fx, inflow, start=start, method=method, profile=profile,
+                                t0=t0, t_end=t_end,
+                                rtol=self.params['rtol'] if rtol is None else rtol,
+                                atol=self.params['atol'] if atol is None else atol,
+                                max_steps=max_steps, newton=steady, newton_iters=newton_iters,
+                                root_dist=float(root_dist) if steady else 0.0,
+                                screen=(float(screen), SCREEN_MARGIN) if (steady and screen) else None,
+                                wave_order=-1)
+        torch = net.torch
+        tin = torch.as_tensor(np.asarray(inflow, float), dtype=torch.float64, device='cuda') \
+            if not torch.is_tensor(inflow) else inflow.to(dtype=torch.float64, device='cuda')
+        if tin.dim() == 1:
+            tin = tin[:, None].expand(len(plan.dyn), n)
+        out['conversion'] = {}
+        for i, name in enumerate(plan.dyn):
+            if flow[i] != 0.0 and bool((tin[i] > 0.0).all()):
+                out['conversion'][name] = 1.0 - out['y'][i] / tin[i]
+        if to_numpy:
+            return {k: ({s: v.cpu().numpy() for s, v in x.items()} if isinstance(x, dict) else x.cpu().numpy())
+                    for k, x in out.items()}
         return out
 
     def drc_batch(self, tof_terms, T=None, p=None, desc=None, eps=1.0e-3, steady=False, t_end=None, rtol=None,
@@ -1324,6 +1427,7 @@ class System:
     def solve_odes(self):
         """old_system.py:315-383: integrate params['times'][0] -> [-1]; self.times /
         self.solution hold the state at output_times() (device dense output)."""
+        self._refuse_pfr('solve_odes')
         plan = self.plan()
         times = self.output_times()
         inside = times[times >= float(self.params['times'][0])]
@@ -1389,6 +1493,7 @@ class System:
         """old_system.py:385-468 find_steady(store_steady, plot_comparison, path) for
         formulation 'classic'; system.py:566-639 find_steady(max_iters, y0, method)
         -> SteadyStateResults for formulation 'patched'."""
+        self._refuse_pfr('find_steady')
         if self.formulation == 'patched':
             return self.find_steady_state(*args, **kw)
         return self._find_steady_classic(*args, **kw)

@@ -8,6 +8,7 @@
 // they are launched, as before.
 #pragma once
 #include "mk_group.h"
+#include "mk_cascade.h"
 
 // k_solve over the runtime plan of NS = 1..8 dynamic species, with the
 // evaluation kernels of the same NS
@@ -17,6 +18,8 @@
 // lane-group kernels: (NSP, G, P) of PCK_GRP_SWITCH
 #define PCK_INST_GRP(X) X(16, 16, 1) X(32, 32, 1) X(64, 64, 1)
 
+// k_cascade (mk_cascade.h): the runtime plans of PCK_INST_LANE_RT and the
+// compiled-in plans of PCK_INST_CASCADE_CT
 #define PCK_SIG_SOLVE NetView, CondView, const double*, const double*, int64_t, SolveArgs
 #define PCK_SIG_RATES NetView, CondView, const double*, const double*, int64_t, const double*, int64_t, double*
 #define PCK_SIG_SOLVE_GRP NetView, GrpView, CondView, const double*, const double*, int64_t, SolveArgs, GrpArgs
@@ -29,6 +32,9 @@
     EXT template __global__ void k_species_rates<N, false>(PCK_SIG_RATES);        \
     EXT template __global__ void k_jacobian<N>(PCK_SIG_RATES);
 #define PCK_DO_LANE_CT(EXT, id, T) EXT template __global__ void k_solve<PlanCT<T>, false>(PCK_SIG_SOLVE);
+#define PCK_SIG_CASCADE NetView, CondView, const double*, const double*, int64_t, SolveArgs, CascadeArgs
+#define PCK_DO_CASCADE_RT(EXT, N) EXT template __global__ void k_cascade<PlanRT<N>>(PCK_SIG_CASCADE);
+#define PCK_DO_CASCADE_CT(EXT, id, T) EXT template __global__ void k_cascade<PlanCT<T>>(PCK_SIG_CASCADE);
 #define PCK_DO_GRP(EXT, NP, GG, PP)                                                      \
     EXT template __global__ void k_solve_grp<NP, GG, PP>(PCK_SIG_SOLVE_GRP);              \
     EXT template __global__ void k_rates_grp<NP, GG, PP>(PCK_SIG_RATES_GRP);

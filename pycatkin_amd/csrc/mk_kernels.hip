@@ -50,6 +50,7 @@ struct pck_network {
     int sens_mode = PCK_SENS_LANES_GROUP;         // pck_network_set_sens_lanes
     int multi_mode = PCK_SENS_LANES_GROUP;        // pck_network_set_multi_lanes
     mutable std::atomic<int> sens_lanes{0};       // lanes per condition of the last adjoint launch
+    int has_flow = 0;                             // a dynamic row has a flow rate (pck_solve_cascade needs one)
 };
 
 // FNV-1a 64 over the solver-side structure (network.py: structural_digest)
@@ -265,6 +266,7 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 #include "mk_sens_lane.h"
 #include "mk_sens_multi.h"
 #include "mk_sens_multi_lane.h"
+#include "mk_cascade.h"
 
 // The solver kernels are compiled in translation units of their own in the
 // product build (csrc/mk_inst.h, csrc/tu_*.hip): here they are only declared.
@@ -288,6 +290,12 @@ PCK_COMPILED_NETWORKS(PCK_X)
 #undef PCK_X
 #define PCK_X(NP, GG, PP) PCK_DO_GRP(extern, NP, GG, PP)
 PCK_INST_GRP(PCK_X)
+#undef PCK_X
+#define PCK_X(N) PCK_DO_CASCADE_RT(extern, N)
+PCK_INST_LANE_RT(PCK_X)
+#undef PCK_X
+#define PCK_X(id, T) PCK_DO_CASCADE_CT(extern, id, T)
+PCK_INST_CASCADE_CT(PCK_X)
 #undef PCK_X
 }  // namespace pck
 #endif
@@ -628,6 +636,8 @@ extern "C" int pck_network_create(const int32_t* ip, int64_t n_ip, const double*
         h = fnv1a(h, dp + doff[PCK_D_CONS], sizeof(double) * nv.NCONS * nv.NDYN);
         h = fnv1a(h, ip + ocp, sizeof(int32_t) * nv.NCONS);
         net->digest = h;
+        for (int i = 0; i < nv.NDYN; ++i)
+            if (dp[doff[PCK_D_DYN] + 4 * i + 3] != 0.0) net->has_flow = 1;
 #define PCK_MATCH(id, T) \
         if (h == T::DIGEST && nv.NDYN == T::NS && nv.NRXN == T::R && nv.NCONS == T::NCONS) net->spec = id;
         PCK_COMPILED_NETWORKS(PCK_MATCH)
@@ -1495,6 +1505,118 @@ extern "C" int pck_solve(const pck_network* net, const pck_conditions* cond, con
         HIPCHK(hipMemcpy2DAsync(out->kr, sizeof(double) * out->ld_k, kb + (int64_t)(R > 0 ? R : 1) * cond->n,
                                 sizeof(double) * cond->n, sizeof(double) * cond->n, R, hipMemcpyDeviceToDevice,
                                 (hipStream_t)stream));
+    }
+    return PCK_OK;
+}
+
+// Reactor cascade (mk_cascade.h): rate constants once, then one launch of
+// k_cascade in which every lane marches its condition through the cells.
+extern "C" int pck_solve_cascade(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                                 const pck_cascade* cas, const pck_outputs* out, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    if (use_group(net, 1) || cascade_lds_bytes(net->nv.NRXN, net->nv.NDYN, PCK_SOLVE_BLOCK) > 64 * 1024)
+        return fail(PCK_E_SIZE, "reactor cascade: the one-lane solver only (at most %s%lld dynamic species)", "",
+                    PCK_MAX_DYN_LANE);
+    rc = check_params(prm);
+    if (rc) return rc;
+    if (!cas || !out) return fail(PCK_E_ARG, "null cascade/outputs%s", "");
+    if (cas->cells < 1 || cas->cells > PCK_MAX_CELLS)
+        return fail(PCK_E_ARG, "cells%s must be in 1..%lld", "", PCK_MAX_CELLS);
+    if (cas->start != PCK_CASCADE_START_Y0 && cas->start != PCK_CASCADE_START_UPSTREAM)
+        return fail(PCK_E_ARG, "unknown cascade start mode%s %lld", "", cas->start);
+    if (prm->t_out || prm->n_out > 0 || out->traj)
+        return fail(PCK_E_ARG, "reactor cascade: no trajectory output%s", "");
+    if (prm->retry_rtol != 0.0) return fail(PCK_E_ARG, "reactor cascade: no retry pass (retry_rtol must be 0)%s", "");
+    if (prm->want_activity) return fail(PCK_E_ARG, "reactor cascade: TOF only (want_activity must be 0)%s", "");
+    if (!net->has_flow)
+        return fail(PCK_E_ARG, "reactor cascade: the network has no flow row (every cell would be the same)%s", "");
+    const int64_t n = cond->n;
+    if (out->y && out->ld_y < n) return fail(PCK_E_ARG, "ld_y%s too small", "");
+    if (cas->y_cells && cas->ld_yc < n) return fail(PCK_E_ARG, "ld_yc%s too small", "");
+    if ((cas->tof_cells || cas->status_cells || cas->nsteps_cells) && cas->ld_c < n)
+        return fail(PCK_E_ARG, "ld_c%s too small", "");
+    if ((out->kf || out->kr) && n > 0 && (out->ld_k < n || !out->kf || !out->kr))
+        return fail(PCK_E_ARG, "kf/kr dump needs both arrays%s", "");
+    if (n == 0) return PCK_OK;
+    if (!cond->y0) return fail(PCK_E_ARG, "initial state y0 required%s", "");
+    hipStream_t s = (hipStream_t)stream;
+    const int R = net->nv.NRXN;
+    StreamScratch kscr;
+    rc = salloc(kscr, sizeof(double) * 2 * (size_t)(R > 0 ? R : 1) * n, s);
+    if (rc) return rc;
+    double* kf = kscr.as<double>();
+    double* kr = kf + (int64_t)(R > 0 ? R : 1) * n;
+    rc = launch_rate_constants(net, cond, kf, kr, n, s);
+    if (rc) return rc;
+    // the per-cell rule's parameters, as launch_solve sets them for pck_solve
+    SolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = out->y; a.ld_y = out->ld_y; a.tof = out->tof; a.status = out->status; a.nsteps = out->nsteps;
+    a.G = 1;
+    a.t0 = prm->t0; a.t_end = prm->t_end; a.rtol = prm->rtol; a.atol = prm->atol; a.eps = prm->drc_eps;
+    a.max_steps = prm->max_steps; a.newton = prm->newton; a.newton_iters = prm->newton_iters;
+    a.root_dist = prm->root_dist;
+    {
+        const char* e = getenv("PCK_CONS_ROWS");
+        a.cons_rows = (e && e[0] == '1');
+    }
+    {
+        a.screen_max_steps = std::min(a.max_steps, 2000);
+        const char* e = getenv("PCK_SCREEN_MAX_STEPS");
+        if (e && atoi(e) > 0) a.screen_max_steps = std::min(a.max_steps, atoi(e));
+    }
+    if (prm->newton && prm->root_dist > 0.0 && prm->screen_rtol > 0.0 && prm->screen_rtol > prm->rtol) {
+        a.screen_rtol = prm->screen_rtol;
+        a.screen_atol = a.atol * (prm->screen_rtol / a.rtol);
+        a.screen_dist = a.root_dist * (prm->screen_margin > 0.0 ? prm->screen_margin : 0.1);
+    }
+    CascadeArgs ca;
+    ca.cells = cas->cells; ca.start = cas->start;
+    ca.y_cells = cas->y_cells; ca.ld_yc = cas->ld_yc;
+    ca.tof_cells = cas->tof_cells; ca.status_cells = cas->status_cells; ca.nsteps_cells = cas->nsteps_cells;
+    ca.ld_c = cas->ld_c;
+    ca.cell_fail = cas->cell_fail;
+    const int B = PCK_SOLVE_BLOCK;
+    const size_t shm = cascade_lds_bytes(R, net->nv.NDYN, B);
+    const int64_t nb = (n + B - 1) / B;
+    if (nb > 0x7fffffffLL) return fail(PCK_E_SIZE, "reactor cascade: more than 2^31 - 1 workgroups%s", "");
+    dim3 g((unsigned)nb);
+    bool done = false;
+    if (net->spec && net->plan_mode == PCK_PLAN_AUTO) {
+#define PCK_LAUNCH_CT(id, T)                                                                                   \
+        if (net->spec == id) {                                                                                \
+            hipLaunchKernelGGL(k_cascade<PlanCT<T>>, g, dim3(B), shm, s, net->nv, cview(cond), kf, kr, n, a, ca); \
+            done = true;                                                                                      \
+        }
+        PCK_INST_CASCADE_CT(PCK_LAUNCH_CT)
+#undef PCK_LAUNCH_CT
+    }
+    if (!done) {
+        hipFunction_t f = nullptr;
+        if (net->plan_mode == PCK_PLAN_AUTO && !net->jit_src.empty() && jit_enabled())
+            f = jit_cascade_kernel(net->digest, net->jit_src);
+        net->jit_on.store(f != nullptr, std::memory_order_relaxed);
+        if (f) {
+            NetView nv = net->nv;
+            CondView cv = cview(cond);
+            const double* kfp = kf;
+            const double* krp = kr;
+            int64_t ldk = n;
+            void* args[] = {&nv, &cv, &kfp, &krp, &ldk, &a, &ca};
+            HIPCHK(hipModuleLaunchKernel(f, g.x, 1, 1, B, 1, 1, (unsigned)shm, s, args, nullptr));
+        } else {
+#define CALL(N) hipLaunchKernelGGL(k_cascade<PlanRT<N>>, g, dim3(B), shm, s, net->nv, cview(cond), kf, kr, n, a, ca)
+            PCK_NS_SWITCH(net->nv.NDYN, CALL)
+#undef CALL
+        }
+    }
+    HIPCHK(hipGetLastError());
+    if (out->kf || out->kr) {
+        HIPCHK(hipMemcpy2DAsync(out->kf, sizeof(double) * out->ld_k, kf, sizeof(double) * n, sizeof(double) * n, R,
+                                hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(out->kr, sizeof(double) * out->ld_k, kr, sizeof(double) * n, sizeof(double) * n, R,
+                                hipMemcpyDeviceToDevice, s));
     }
     return PCK_OK;
 }

@@ -310,6 +310,126 @@ class DeviceNetwork:
         L.check(self.lib.pck_solve(self.h, C.byref(c), C.byref(prm), C.byref(o), _stream(torch)))
         return out
 
+    def _cascade_out(self, n, cells, profile, want_k):
+        torch = self.torch
+        out = dict(y=torch.empty((self.NDYN, n), dtype=torch.float64, device='cuda'),
+                   tof=torch.empty(n, dtype=torch.float64, device='cuda'),
+                   status=torch.empty(n, dtype=torch.int32, device='cuda'),
+                   nsteps=torch.empty(n, dtype=torch.int32, device='cuda'),
+                   cell_fail=torch.empty(n, dtype=torch.int32, device='cuda'))
+        if profile:
+            out['y_cells'] = torch.empty((cells, self.NDYN, n), dtype=torch.float64, device='cuda')
+            out['tof_cells'] = torch.empty((cells, n), dtype=torch.float64, device='cuda')
+            out['status_cells'] = torch.empty((cells, n), dtype=torch.int32, device='cuda')
+            out['nsteps_cells'] = torch.empty((cells, n), dtype=torch.int32, device='cuda')
+        if want_k:
+            out['kf'] = torch.empty((self.NRXN, n), dtype=torch.float64, device='cuda')
+            out['kr'] = torch.empty_like(out['kf'])
+        return out
+
+    def solve_cascade(self, n, T, p, y0, cells, desc=None, fixc=None, inflow=None, start='system', method='fused',
+                      profile=True, want_k=False, t_out=None, **kw):
+        """pck_solve_cascade: `cells` CSTR cells in series per condition, cell c
+        fed by cell c-1 (cell 0 by `inflow`), each solved by the rule of solve
+        with the parameters **kw (params); the network's coefficients are one
+        cell's.  start: 'system' (every cell's transient from y0) or
+        'upstream' (from the cell before).  method: 'fused' (one launch, the
+        one-lane solver only) or 'loop' (`cells` calls of solve with device
+        tensors, any kernel family).  Returns dict(y [NS,n] the outlet, tof
+        [n] the mean cell TOF, status, nsteps [n], cell_fail [n], -1 where no
+        cell failed) and, with profile, y_cells [cells,NS,n], tof_cells,
+        status_cells, nsteps_cells [cells,n].  (start may also be the integer
+        of pck_cascade.start; t_out is passed on for the library to refuse.)"""
+        torch = self.torch
+        if isinstance(start, str) and start not in L.CASCADE_START_MODES:
+            raise ValueError("start must be 'system' or 'upstream', not %r" % (start,))
+        start = L.CASCADE_START_MODES[start] if isinstance(start, str) else int(start)
+        if method not in ('fused', 'loop'):
+            raise ValueError("method must be 'fused' or 'loop', not %r" % (method,))
+        cells = int(cells)
+        if method == 'loop':
+            return self._cascade_loop(n, T, p, y0, cells, desc, fixc, inflow, start, profile, want_k, kw)
+        c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)
+        prm = self.params(**kw)
+        if t_out is not None:
+            tt = torch.as_tensor(np.asarray(t_out, float).ravel(), dtype=torch.float64, device='cuda').contiguous()
+            keep.append(tt)
+            prm.t_out, prm.n_out = _ptr(tt).value, int(tt.numel())
+        # sized for the refusals too (cells out of range is the library's to refuse)
+        out = self._cascade_out(n, min(max(cells, 1), L.MAX_CELLS), profile, want_k)
+        if _POISON:
+            for v in out.values():
+                v.fill_(float('nan') if v.is_floating_point() else -7)
+        o = L.Outputs()
+        o.y, o.ld_y = _ptr(out['y']), n
+        o.tof, o.status, o.nsteps = _ptr(out['tof']), _ptr(out['status']), _ptr(out['nsteps'])
+        if want_k:
+            o.kf, o.kr, o.ld_k = _ptr(out['kf']), _ptr(out['kr']), n
+        cas = L.Cascade()
+        cas.cells, cas.start = cells, start
+        cas.cell_fail = _ptr(out['cell_fail'])
+        if profile:
+            cas.y_cells, cas.ld_yc = _ptr(out['y_cells']), n
+            cas.tof_cells, cas.status_cells = _ptr(out['tof_cells']), _ptr(out['status_cells'])
+            cas.nsteps_cells, cas.ld_c = _ptr(out['nsteps_cells']), n
+        L.check(self.lib.pck_solve_cascade(self.h, C.byref(c), C.byref(prm), C.byref(cas), C.byref(o), _stream(torch)))
+        return out
+
+    def _cascade_loop(self, n, T, p, y0, cells, desc, fixc, inflow, start, profile, want_k, kw):
+        """The march of solve_cascade as `cells` calls of solve, everything on
+        the device: the same rules (pck_solve_cascade), on any kernel family."""
+        torch = self.torch
+        if not 1 <= cells <= L.MAX_CELLS:
+            raise ValueError('cells must be in 1..%d, not %d' % (L.MAX_CELLS, cells))
+        if start not in (L.CASCADE_START_Y0, L.CASCADE_START_UPSTREAM):
+            raise ValueError('unknown cascade start mode %r' % (start,))
+        off = self._dp_off(L.D_DYN)
+        flow = torch.as_tensor(self._dp[off: off + 4 * self.NDYN].reshape(self.NDYN, 4)[:, 3] != 0.0, device='cuda')
+        if not bool(flow.any()):
+            raise ValueError('reactor cascade: the network has no flow row (every cell would be the same)')
+        if inflow is None:
+            raise ValueError('reactor cascade: inflow required')
+        out = self._cascade_out(n, cells, True, want_k)
+        ti, _, _ = self._mat(inflow, self.NDYN, n, 'inflow')
+        ty, _, _ = self._mat(y0, self.NDYN, n, 'y0')
+        cur_in = (ti[:, None].expand(self.NDYN, n) if ti.dim() == 1 else ti).clone()
+        cur_y0 = (ty[:, None].expand(self.NDYN, n) if ty.dim() == 1 else ty).clone()
+        nan = float('nan')
+        fail = torch.zeros(n, dtype=torch.int32, device='cuda')
+        out['cell_fail'].fill_(-1)
+        for cell in range(cells):
+            r = self.solve(n, T, p, cur_y0, desc, fixc, cur_in, want_k=want_k and cell == 0, **kw)
+            if want_k and cell == 0:
+                out['kf'], out['kr'] = r['kf'], r['kr']
+            dead = fail != 0
+            st = torch.where(dead, fail, r['status'])
+            newfail = (~dead) & (st >= L.ST_MAXSTEPS) & (st <= L.ST_NONFINITE)
+            out['y_cells'][cell] = torch.where(dead[None, :], torch.full_like(r['y'], nan), r['y'])
+            out['tof_cells'][cell] = torch.where(dead, torch.full_like(r['tof'], nan), r['tof'])
+            out['status_cells'][cell] = st
+            out['nsteps_cells'][cell] = torch.where(dead, torch.zeros_like(r['nsteps']), r['nsteps'])
+            out['cell_fail'][newfail] = cell
+            fail = torch.where(newfail, st, fail)
+            go = (fail == 0)
+            out['y'][:, ~dead] = r['y'][:, ~dead]
+            upd = go[None, :] & flow[:, None]
+            cur_in = torch.where(upd, r['y'], cur_in)
+            if start == L.CASCADE_START_UPSTREAM:
+                cur_y0 = torch.where(go[None, :], r['y'], cur_y0)
+        stc = out['status_cells']
+        out['status'] = torch.where(fail != 0, fail, (stc == L.ST_NEWTON).any(0).to(torch.int32) * L.ST_NEWTON)
+        out['nsteps'] = out['nsteps_cells'].sum(0, dtype=torch.int32)
+        out['tof'] = out['tof_cells'].sum(0) / cells           # NaN where the march stopped
+        out['tof'] = torch.where(fail != 0, torch.full_like(out['tof'], nan), out['tof'])
+        if not profile:
+            for k in ('y_cells', 'tof_cells', 'status_cells', 'nsteps_cells'):
+                del out[k]
+        return out
+
+    def _dp_off(self, blk):
+        """Offset of block `blk` (L.D_*) in the plan's double blob."""
+        return int(self._ip[L.I_HDR + blk])
+
     def drc(self, n, T, p, y0, desc=None, fixc=None, inflow=None, **kw):
         torch = self.torch
         c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)

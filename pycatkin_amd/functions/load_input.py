@@ -7,7 +7,7 @@ import os
 
 from ..classes.energy import Energy
 from ..classes.reaction import Reaction, ReactionDerivedReaction, UserDefinedReaction
-from ..classes.reactor import CSTReactor, InfiniteDilutionReactor
+from ..classes.reactor import CSTReactor, InfiniteDilutionReactor, PFReactor
 from ..classes.state import ScalingState, State
 from ..classes.system import System
 from ..constants.physical_constants import bartoPa
@@ -95,8 +95,10 @@ def read_from_input_file(input_path='input.json', base_system=None, base_dir=Non
             sim.add_reactor(InfiniteDilutionReactor())
         elif 'CSTReactor' in rx:
             sim.add_reactor(CSTReactor(**rx['CSTReactor']))
+        elif 'PFReactor' in rx:
+            sim.add_reactor(PFReactor(**rx['PFReactor']))
         else:
-            raise TypeError('Unknown reactor option, please choose InfiniteDilutionReactor or CSTReactor.')
+            raise TypeError('Unknown reactor option, please choose InfiniteDilutionReactor, CSTReactor or PFReactor.')
     elif sim.reactions:
         raise RuntimeError('Cannot consider reactions without reactor. To use constant boundary conditions, '
                            'please specify InfiniteDilutionReactor.')

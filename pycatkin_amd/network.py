@@ -165,7 +165,7 @@ def compile_system(system, tof_terms=(), descriptors=None, rate_model=None):
                     gas.add(s.name)
         ads_l = [s for s in species if s in ads]
         gas_l = [s for s in species if s in gas]
-        cstr = system.reactor is not None and type(system.reactor).__name__ == 'CSTReactor'
+        cstr = system.reactor is not None and type(system.reactor).__name__ in ('CSTReactor', 'PFReactor')
         dyn = ads_l + (gas_l if cstr else [])
         fix = [] if cstr else gas_l
     elif formulation == 'patched':
