@@ -538,6 +538,53 @@ int pck_drc_multi_adjoint(const pck_network* net, const pck_conditions* cond, co
  * of the two entry points are the same in every mode. */
 int pck_network_set_multi_lanes(pck_network* net, int mode);
 
+/* Bed DRC (csrc/mk_cascade_adjoint.h): the degree of rate control of K objectives of a
+ * reactor cascade of `cells` cells (pck_solve_cascade) at given cell states, by one
+ * backward adjoint sweep through the cells in one launch, one lane per condition
+ * (networks of up to PCK_MAX_DYN_LANE dynamic species).  pck_multi_obj is read for a bed as
+ *   J_m = (1/cells) sum_c sum_j wr[m][j] net_j(y_c) + sum_i wy[m][i] y_{cells-1,i}:
+ * wr weights the bed mean of the net rates (with the TOF terms: the tof of
+ * pck_solve_cascade), wy the outlet state.  With F(y_c, u_c, k) = 0 the steady equations
+ * of cell c as pck_drc_multi_at poses them (u_c its inflow: cond->inflow for c = 0, the
+ * state of cell c-1 on the flow rows else), A_c = dF/dy, w_{c,i} the row scale and
+ * phi_{c,i} the flow rate of row i, each 0 where row i of cell c was replaced,
+ *   A_c^T mu_{m,c} = dJ_m/dy_c - phi_{c+1} (.) mu_{m,c+1}      c = cells-1 ... 0,  mu_{m,cells} = 0
+ *   xi[m][j] = sum_c net_j(y_c) (wr[m][j] / cells - sum_i mu_{m,c,i} w_{c,i} S_ij) / J_m
+ *   order_in[m][i] = -mu_{m,0,i} phi_{0,i} inflow_i / J_m      (d ln J_m / d ln inflow_i)
+ * double-double throughout; for cells = 1 this is pck_drc_multi_at (one-lane kernel) term
+ * for term.  y_cells [cells][NDYN][ld_yc] as pck_solve_cascade writes it; status_cells
+ * [cells][ld_c] (optional): a condition is computed only if every cell is PCK_ST_OK, else
+ * it keeps its bed status as pck_solve_cascade reports it (the first failing status in cell order,
+ * else PCK_ST_NEWTON) and gets NaN in every xi and order_in and that status in every ostatus.  order_in [K * NDYN][ld_oi]
+ * (optional), row m * NDYN + i.  pck_multi_out as for pck_drc_multi_at: val[m] = J_m for
+ * every condition whose cell states are all finite, NaN otherwise; status
+ * PCK_ST_SENS_SINGULAR for a zero pivot or a non-finite factor in any cell; ostatus[m]
+ * PCK_ST_NONFINITE for a zero or non-finite J_m or an adjoint solve that overflows, which
+ * fails that objective alone.  A condition's result does not depend on the batch.
+ * PCK_E_SIZE: more than PCK_MAX_DYN_LANE dynamic species, or a network beyond the
+ * lane-group records (as pck_drc_at).  PCK_E_ARG: cells outside 1..PCK_MAX_CELLS, a network
+ * without a flow row, K < 1, NULL obj / out / val / xi, wr and wy both NULL, a leading
+ * dimension below n.  n == 0 returns PCK_OK.
+ * Device memory: the call allocates, on the stream and for its own length, a workspace of
+ * 16 K (NDYN + NRXN + 2) n bytes (what a lane carries from cell to cell), whatever `cells`
+ * is; PCK_E_HIP if that does not fit.  Results do not depend on the batch, so a large
+ * batch may be split into calls. */
+int pck_cascade_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                       int64_t ld_k, const double* y_cells, int64_t ld_yc, int32_t cells,
+                       const int32_t* status_cells, int64_t ld_c, const pck_multi_obj* obj,
+                       const pck_multi_out* out, double* order_in, int64_t ld_oi, void* stream);
+
+/* pck_solve_cascade (prm->newton = 1 required; cas->start as given) and then
+ * pck_cascade_drc_at at its cell states, with the solve's own rate constants.  cas: the
+ * per-cell outputs are written as by pck_solve_cascade; y_cells and status_cells are
+ * allocated per call where they are NULL.  nsteps (optional): the steps summed over the
+ * cells.  A bed with a cell that did not report a reached root keeps that status and gets
+ * NaN xi.  PCK_E_ARG: prm->newton == 0, and what pck_solve_cascade and pck_cascade_drc_at
+ * refuse. */
+int pck_cascade_drc(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                    const pck_cascade* cas, const pck_multi_obj* obj, const pck_multi_out* out,
+                    double* order_in, int64_t ld_oi, int32_t* nsteps, void* stream);
+
 /* An energy landscape (energy.py:12 Energy.minima): n_pts entries along the
  * reaction coordinate, 4 <= n_pts <= PCK_MAX_PES, each the energy-program
  * register that holds its energy (eV).  Entry 0 is the reference every energy

@@ -19,7 +19,11 @@ EXPORTED = ('pck_abi_version', 'pck_last_error', 'pck_network_create', 'pck_netw
             'pck_reaction_rates', 'pck_jacobian', 'pck_solve', 'pck_solve_cascade', 'pck_drc', 'pck_energy_span', 'pck_ensemble_noise',
             'pck_ensemble_stats', 'pck_drc_at', 'pck_drc_adjoint', 'pck_sens_at', 'pck_sens_adjoint',
             'pck_network_set_sens_lanes', 'pck_network_sens_lanes', 'pck_drc_multi_at', 'pck_drc_multi_adjoint',
-            'pck_network_set_multi_lanes', 'pck_eigvals', 'pck_stability_at', 'pck_stability')
+            'pck_network_set_multi_lanes', 'pck_eigvals', 'pck_stability_at', 'pck_stability', 'pck_cascade_drc_at',
+            'pck_cascade_drc')
+# entry points added without a new ABI version: a library built before them still loads, and the call that
+# needs one says so (engine.py)
+OPTIONAL = ('pck_cascade_drc_at', 'pck_cascade_drc')
 
 ABI_VERSION = 10
 
@@ -182,7 +186,15 @@ def load():
     lib.pck_energy_span.argtypes = [vp, C.POINTER(Conditions), C.POINTER(Landscape), C.POINTER(SpanOutputs), vp]
     lib.pck_ensemble_noise.argtypes = [C.c_uint64, C.c_uint64, i64, i64, i64, C.c_int, C.c_double, C.c_double, vp, i64, vp]
     lib.pck_ensemble_stats.argtypes = [vp, i64, i64, vp, C.c_uint32, i64, i64, i64, C.POINTER(EnsStats), vp]
+    if hasattr(lib, 'pck_cascade_drc_at'):
+        lib.pck_cascade_drc_at.argtypes = [vp, C.POINTER(Conditions), vp, vp, i64, vp, i64, C.c_int32, vp, i64,
+                                           C.POINTER(MultiObj), C.POINTER(MultiOut), vp, i64, vp]
+    if hasattr(lib, 'pck_cascade_drc'):
+        lib.pck_cascade_drc.argtypes = [vp, C.POINTER(Conditions), C.POINTER(SolveParams), C.POINTER(Cascade),
+                                        C.POINTER(MultiObj), C.POINTER(MultiOut), vp, i64, vp, vp]
     for name in EXPORTED:
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         if name not in ('pck_last_error',):
             getattr(lib, name).restype = C.c_int
     _lib = lib

@@ -586,12 +586,151 @@ class System:
             return {k: v.cpu().numpy() for k, v in out.items()}
         return out
 
-    def _refuse_pfr(self, what):
+    def _refuse_pfr(self, what, instead='solve_cascade_batch', verb='solves'):
         """A PFReactor's coefficients are one cell's: the single-reactor calls
         would silently answer for one cell of the bed."""
         if isinstance(self.reactor, PFReactor):
-            raise ValueError('%s solves a single stirred tank; a PFReactor (%d cells) is solved by '
-                             'solve_cascade_batch' % (what, self.reactor.cells))
+            raise ValueError('%s %s a single stirred tank; a PFReactor (%d cells) is %s by '
+                             '%s' % (what, verb, self.reactor.cells, 'solved' if verb == 'solves' else 'analysed',
+                                     instead))
+
+    def _cascade_cells(self, cells):
+        """The cell count of a bed call: the PFReactor's, or the caller's."""
+        if cells is None:
+            if not isinstance(self.reactor, PFReactor):
+                raise ValueError('cells is required unless the reactor is a PFReactor')
+            cells = self.reactor.cells
+        if isinstance(cells, bool) or int(cells) != cells or not 1 <= int(cells) <= _L.MAX_CELLS:
+            raise ValueError('cells must be an integer in 1..%d, not %r' % (_L.MAX_CELLS, cells))
+        cells = int(cells)
+        if isinstance(self.reactor, PFReactor) and cells != self.reactor.cells:
+            raise ValueError('cells=%d differs from the PFReactor\'s %d (its flow rate is one cell\'s)'
+                             % (cells, self.reactor.cells))
+        return cells
+
+    def _bed_objectives(self, plan, tof_terms, outlet, wr, wy):
+        """(labels, wr [K, active reactions], wy [K, dynamic species]) of a bed
+        DRC call: the bed-mean TOF of tof_terms, one outlet concentration per
+        name in `outlet`, then the rows of wr / wy as given."""
+        obs = []
+        if tof_terms:
+            obs.append({'rates': {}, 'label': 'tof'})
+            for name in tof_terms:
+                obs[0]['rates'][name] = obs[0]['rates'].get(name, 0.0) + 1.0
+        for name in ([outlet] if isinstance(outlet, str) else list(outlet or ())):
+            obs.append({'species': {name: 1.0}, 'label': 'outlet[%s]' % name})
+        labels, a, b = self._objectives(plan, obs) if obs else ([], np.zeros((0, len(plan.reactions))),
+                                                                np.zeros((0, len(plan.dyn))))
+        if wr is not None or wy is not None:
+            xr = None if wr is None else np.atleast_2d(np.asarray(wr, float))
+            xy = None if wy is None else np.atleast_2d(np.asarray(wy, float))
+            K = (xr if xr is not None else xy).shape[0]
+            xr = np.zeros((K, len(plan.reactions))) if xr is None else xr
+            xy = np.zeros((K, len(plan.dyn))) if xy is None else xy
+            if xr.shape != (K, len(plan.reactions)) or xy.shape != (K, len(plan.dyn)):
+                raise ValueError('wr / wy must be [K, %d] / [K, %d] (plan.reactions / plan.dyn order)'
+                                 % (len(plan.reactions), len(plan.dyn)))
+            labels = labels + ['w%d' % m for m in range(K)]
+            a, b = np.vstack([a, xr]), np.vstack([b, xy])
+        if not labels:
+            raise ValueError('no objectives: give tof_terms, outlet, wr or wy')
+        return labels, a, b
+
+    def _bed_net(self, what):
+        """(plan, device network) of a bed DRC call: a reactor with flow and at
+        most MAX_DYN_LANE dynamic species."""
+        plan = self.plan((), None)
+        off = int(plan.ip[_L.I_HDR + _L.D_DYN])
+        flow = np.asarray(plan.dp[off: off + 4 * len(plan.dyn)]).reshape(len(plan.dyn), 4)[:, 3]
+        if not np.any(flow != 0.0):
+            raise ValueError('%s needs a reactor with flow (CSTReactor or PFReactor)' % what)
+        if len(plan.dyn) > _L.MAX_DYN_LANE:
+            raise ValueError('%s runs on the one-lane adjoint kernel: at most %d dynamic species (this network '
+                             'has %d)' % (what, _L.MAX_DYN_LANE, len(plan.dyn)))
+        return plan, self.device((), None)
+
+    def _bed_dict(self, plan, labels, r, n):
+        out = self._multi_dict(plan, labels, r, n)
+        if 'order_in' in r:
+            out['order_in'] = r['order_in'].cpu().numpy()
+        for key in ('cell_fail', 'y_cells', 'status_cells'):
+            if key in r:
+                out[key] = r[key].cpu().numpy()
+        return out
+
+    def cascade_drc_at(self, Y_cells, tof_terms=(), outlet=None, wr=None, wy=None, T=None, p=None, desc=None,
+                       fix=None, inflow=None, status_cells=None, k=None):
+        """The degree of rate control of a catalyst bed at given cell states
+        Y_cells [cells, n_dynamic, n] (plan.dyn order; solve_cascade_batch's
+        'y_cells'), without a solve: one backward adjoint sweep through the
+        cells per condition, in one launch (pck_cascade_drc_at; DESIGN.md "Bed
+        DRC").  Objectives as in cascade_drc_batch.  status_cells [cells, n]
+        (optional): a bed is computed only if every cell's status is 0, else it
+        keeps its bed status (the first failing cell's, else 4) and gets NaN.  k = (kf, kr) as in drc_at.
+        Returns dict(labels, reactions, val [K, n], xi [K, R, n], order_in
+        [K, NS, n], status [n], ostatus [K, n])."""
+        plan, net = self._bed_net('cascade_drc_at')
+        labels, a, b = self._bed_objectives(plan, tuple(tof_terms), outlet, wr, wy)
+        Y = np.asarray(Y_cells, float)
+        if Y.ndim == 2:
+            Y = Y[:, :, None]
+        if Y.ndim != 3 or Y.shape[1] != net.NDYN:
+            raise ValueError('Y_cells must be [cells, %d, n]' % net.NDYN)
+        self._cascade_cells(Y.shape[0])
+        n = Y.shape[2]
+        T, p, d, fx, _, inflow = self._inputs(net, plan, n, T, p, desc, None, fix, inflow)
+        kf, kr = net.rate_constants(n, T, p, d) if k is None else k
+        r = net.cascade_drc_at(n, T, p, Y, kf, kr, a, b, d, fx, inflow, status_cells)
+        return self._bed_dict(plan, labels, r, n)
+
+    def cascade_drc_batch(self, cells=None, tof_terms=(), outlet=None, wr=None, wy=None, T=None, p=None, desc=None,
+                          y0=None, fix=None, inflow=None, t_end=None, rtol=None, atol=None, max_steps=200000,
+                          newton_iters=60, screen='auto', start='system'):
+        """Which rate constants control a catalyst bed: solve_cascade_batch
+        (steady, method='fused') and then the adjoint sweep of cascade_drc_at at
+        its cell states, with the solve's own rate constants (pck_cascade_drc;
+        DESIGN.md "Bed DRC").  Objectives, in this order: tof_terms gives the
+        bed-mean TOF (solve_cascade_batch's 'tof'); outlet=['CO', ...] one
+        outlet-concentration objective per species; wr [K, active reactions] /
+        wy [K, dynamic species] further weighted objectives (bed mean of the net
+        rates / outlet state).  xi[m, j] = d ln J_m / d ln k_j at fixed K_j;
+        order_in[m, i] = d ln J_m / d ln inflow_i.  For a fed species with inflow
+        y_in and outlet y_out the conversion X = 1 - y_out / y_in has
+        d ln X / d ln k_j = -xi . y_out / (y_in - y_out), xi the outlet
+        objective's.  A bed with a cell that did not report a reached root
+        (status 4) or that failed keeps that status and gets NaN.  Networks of
+        at most 8 dynamic species; a larger one raises.  The remaining arguments
+        are solve_cascade_batch's.  Returns dict(labels, reactions, val [K, n],
+        xi [K, R, n], order_in [K, NS, n], status [n], ostatus [K, n], nsteps
+        [n], cell_fail [n], y_cells [cells, NS, n], status_cells [cells, n])."""
+        if start not in _L.CASCADE_START_MODES:
+            raise ValueError("start must be 'system' or 'upstream', not %r" % (start,))
+        cells = self._cascade_cells(cells)
+        plan, net = self._bed_net('cascade_drc_batch')
+        labels, a, b = self._bed_objectives(plan, tuple(tof_terms), outlet, wr, wy)
+        if desc is not None and not isinstance(desc, dict):
+            n = max(self._n(T, p), int(desc.shape[1]))
+        else:
+            n = self._n(*([T, p] + (list(desc.values()) if desc else [])))
+        for x in (y0, inflow):
+            if x is not None and np.ndim(x) == 2:
+                n = max(n, np.shape(x)[1])
+        T, p, d, fx, y0, inflow = self._inputs(net, plan, n, T, p, desc, y0, fix, inflow)
+        times = self.params['times'] or [0.0, 1.0e4]
+        t0 = times[0]
+        t_end = times[-1] if t_end is None else t_end
+        rtol = STEADY_TRANSIENT[0] if rtol is None else rtol
+        atol = STEADY_TRANSIENT[1] if atol is None else atol
+        root_dist = ROOT_DIST if t_end > t0 else 0.0
+        if isinstance(screen, str):
+            if screen != 'auto':
+                raise ValueError("screen must be 'auto', None or an rtol")
+            screen = SCREEN_RTOL if (root_dist > 0.0 and net.NDYN <= SCREEN_MAX_LANE_SPECIES) else None
+        r = net.cascade_drc(n, T, p, y0, cells, a, b, d, fx, inflow, start=start, t0=t0, t_end=t_end, rtol=rtol,
+                            atol=atol, max_steps=max_steps, newton=True, newton_iters=newton_iters,
+                            root_dist=float(root_dist), screen=(float(screen), SCREEN_MARGIN) if screen else None,
+                            wave_order=-1)
+        return self._bed_dict(plan, labels, r, n)
 
     def solve_cascade_batch(self, cells=None, T=None, p=None, desc=None, y0=None, fix=None, inflow=None,
                             tof_terms=(), steady=True, t_end=None, rtol=None, atol=None, max_steps=200000,
@@ -711,6 +850,7 @@ class System:
 
         Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0', 'status'
         and 'nsteps'."""
+        self._refuse_pfr('drc_batch', 'cascade_drc_batch', 'analyses')
         if method not in ('fd', 'analytic'):
             raise ValueError("method must be 'fd' or 'analytic', not %r" % (method,))
         if method == 'analytic' and not steady:
@@ -774,6 +914,7 @@ class System:
         allows it); the two kernels agree to rounding (DESIGN.md "One-lane
         adjoint").
         Returns {reaction name: xi [n]} (ghost reactions: 0) plus 'tof0' and 'status'."""
+        self._refuse_pfr('drc_at', 'cascade_drc_batch', 'analyses')
         mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan(tuple(tof_terms), None)
         net = self.device(tuple(tof_terms), None)
@@ -882,6 +1023,7 @@ class System:
         get 0), val [K, n] (the objectives' values), xi [K, R, n]
         (d ln J_m / d ln k_j at fixed K_j), status [n], ostatus [K, n] (3: a
         zero or non-finite objective, NaN xi for it alone))."""
+        self._refuse_pfr('drc_objectives_at', 'cascade_drc_batch', 'analyses')
         mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan((), None)
         labels, wr, wy = self._objectives(plan, objectives)
@@ -907,6 +1049,7 @@ class System:
         not report a reached root keeps that status and gets NaN xi.
         adjoint_kernel: as in drc_objectives_at.  Returns what
         drc_objectives_at returns plus 'nsteps'."""
+        self._refuse_pfr('drc_objectives_batch', 'cascade_drc_batch', 'analyses')
         mode = self._adjoint_mode(adjoint_kernel)
         plan = self.plan((), None)
         labels, wr, wy = self._objectives(plan, objectives)

@@ -267,6 +267,7 @@ __global__ void __launch_bounds__(64) k_energy_span(NetView nv, CondView cv, pck
 #include "mk_sens_multi.h"
 #include "mk_sens_multi_lane.h"
 #include "mk_cascade.h"
+#include "mk_cascade_adjoint.h"
 
 // The solver kernels are compiled in translation units of their own in the
 // product build (csrc/mk_inst.h, csrc/tu_*.hip): here they are only declared.
@@ -1905,6 +1906,111 @@ extern "C" int pck_drc_multi_adjoint(const pck_network* net, const pck_condition
     rc = solve_steady(net, cond, prm, nsteps, s, ss);
     if (rc) return rc;
     return launch_multi_at(net, cond, ss.kf, ss.kr, n, ss.y, n, ss.st, obj, out, s);
+}
+
+// ----------------------------------------------------------------------------
+// bed DRC (csrc/mk_cascade_adjoint.h): the multi-objective adjoint swept backward through a cascade's cells
+// ----------------------------------------------------------------------------
+// what pck_cascade_drc_at and pck_cascade_drc refuse: check_multi's list, the one-lane limit, cells, a flow row
+static int check_cascade_drc(const pck_network* net, int64_t n, int cells, const pck_multi_obj* obj,
+                             const pck_multi_out* out, const double* order_in, int64_t ld_oi) {
+    const char* what = "bed DRC";
+    if (!obj || !out) return fail(PCK_E_ARG, "%s: no objectives or no outputs", what);
+    if (obj->K < 1) return fail(PCK_E_ARG, "%s: K < 1", what);
+    if (!obj->wr && !obj->wy) return fail(PCK_E_ARG, "%s: wr and wy are both NULL", what);
+    const int rc = check_adjoint_net(net, what, false);
+    if (rc) return rc;
+    if (net->nv.NDYN > PCK_MAX_DYN_LANE)
+        return fail(PCK_E_SIZE, "%s: the one-lane kernel only (at most %lld dynamic species)", what, PCK_MAX_DYN_LANE);
+    if (cells < 1 || cells > PCK_MAX_CELLS) return fail(PCK_E_ARG, "%s: cells must be in 1..%lld", what, PCK_MAX_CELLS);
+    if (!net->has_flow)
+        return fail(PCK_E_ARG, "%s: the network has no flow row (the cells would not be coupled)", what);
+    if (n == 0) return PCK_OK;
+    if (!out->val || !out->xi) return fail(PCK_E_ARG, "%s: val and xi are required", what);
+    if (out->ld_val < n || out->ld_xi < n || (out->ostatus && out->ld_os < n) || (order_in && ld_oi < n))
+        return fail(PCK_E_ARG, "%s: a leading dimension of the outputs is below n", what);
+    return PCK_OK;
+}
+
+// the workspace (nu, the xi accumulators, the rate sums and the overflow flags: K (NS + R + 2) rows of n
+// double-doubles, 16 K (NS + R + 2) n bytes in one stream-ordered allocation -- 164 MB for Pd111 at n = 262 144,
+// K = 3; a batch too large for it fails with PCK_E_HIP, and since a condition's result does not depend on the
+// batch the caller may split it) and the launch; the checks of check_cascade_drc are done
+static int launch_cascade_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                                 int64_t ld_k, const double* y_cells, int64_t ld_yc, int cells,
+                                 const int32_t* status_cells, int64_t ld_c, const pck_multi_obj* obj,
+                                 const pck_multi_out* out, double* order_in, int64_t ld_oi, hipStream_t s) {
+    const int64_t n = cond->n;
+    if (n == 0) return PCK_OK;
+    const int NS = net->nv.NDYN, R = net->nv.NRXN;
+    StreamScratch ws;
+    int rc = salloc(ws, sizeof(dd) * (size_t)cascade_adjoint_ws_rows(obj->K, NS, R) * (size_t)n, s);
+    if (rc) return rc;
+    const CascadeAdj ca{y_cells, ld_yc, status_cells, ld_c, cells, order_in, ld_oi, ws.as<cadj_v2d>(), n};
+    const MultiObj ob{obj->K, obj->wr, obj->wy};
+    const MultiOut mo{out->val, out->ld_val, out->xi, out->ld_xi, out->status, out->ostatus, out->ld_os};
+    return launch_adjoint(k_bed_adjoint, 64, cascade_adjoint_lds_bytes(NS), net, n, "bed DRC", s, cview(cond), kf, kr,
+                          ld_k, ca, ob, mo);
+}
+
+// d ln J_m / d ln k_j of K bed objectives at given cell states (the reference has none of this).
+extern "C" int pck_cascade_drc_at(const pck_network* net, const pck_conditions* cond, const double* kf, const double* kr,
+                                  int64_t ld_k, const double* y_cells, int64_t ld_yc, int32_t cells,
+                                  const int32_t* status_cells, int64_t ld_c, const pck_multi_obj* obj,
+                                  const pck_multi_out* out, double* order_in, int64_t ld_oi, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    rc = check_cascade_drc(net, cond->n, cells, obj, out, order_in, ld_oi);
+    if (rc) return rc;
+    if (cond->n > 0 && (!kf || !kr || ld_k < cond->n)) return fail(PCK_E_ARG, "bad kf / kr%s", "");
+    if (cond->n > 0 && (!y_cells || ld_yc < cond->n)) return fail(PCK_E_ARG, "bad cell states y_cells%s", "");
+    if (cond->n > 0 && status_cells && ld_c < cond->n) return fail(PCK_E_ARG, "ld_c%s too small", "");
+    return launch_cascade_drc_at(net, cond, kf, kr, ld_k, y_cells, ld_yc, cells, status_cells, ld_c, obj, out, order_in,
+                                 ld_oi, (hipStream_t)stream);
+}
+
+// pck_solve_cascade, then pck_cascade_drc_at at its cell states, with the solve's own rate constants.
+extern "C" int pck_cascade_drc(const pck_network* net, const pck_conditions* cond, const pck_solve_params* prm,
+                               const pck_cascade* cas, const pck_multi_obj* obj, const pck_multi_out* out,
+                               double* order_in, int64_t ld_oi, int32_t* nsteps, void* stream) {
+    int rc = check_cond(net, cond, true);
+    if (rc) return rc;
+    rc = check_adjoint_params(prm, "pck_cascade_drc");
+    if (rc) return rc;
+    if (!cas) return fail(PCK_E_ARG, "null cascade%s", "");
+    const int64_t n = cond->n;
+    rc = check_cascade_drc(net, n, cas->cells, obj, out, order_in, ld_oi);
+    if (rc) return rc;
+    if (n == 0) return PCK_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    const int NS = net->nv.NDYN, R = net->nv.NRXN;
+    // kf | kr of the solve, and the cell states and statuses where the caller keeps none
+    pck_cascade c2 = *cas;
+    const size_t nk = sizeof(double) * 2 * (size_t)R * n;
+    const size_t ny = c2.y_cells ? 0 : sizeof(double) * (size_t)c2.cells * NS * n;
+    // the statuses share ld_c with the caller's tof_cells / nsteps_cells: the buffer is sized by it
+    const bool own_st = !c2.status_cells, shared_ld = c2.tof_cells || c2.nsteps_cells;
+    if (own_st && shared_ld && c2.ld_c < n) return fail(PCK_E_ARG, "ld_c%s too small", "");
+    const int64_t ld_st = shared_ld ? c2.ld_c : n;
+    const size_t nst = own_st ? sizeof(int32_t) * (size_t)c2.cells * (size_t)ld_st : 0;
+    StreamScratch scr;
+    rc = salloc(scr, nk + ny + nst, s);
+    if (rc) return rc;
+    double* kf = scr.as<double>();
+    double* kr = kf + (int64_t)R * n;
+    if (ny) { c2.y_cells = kr + (int64_t)R * n; c2.ld_yc = n; }
+    if (own_st) {
+        c2.status_cells = (int32_t*)((char*)scr.p + nk + ny);
+        c2.ld_c = ld_st;
+    }
+    pck_outputs so;
+    memset(&so, 0, sizeof(so));
+    so.nsteps = nsteps;
+    so.kf = kf; so.kr = kr; so.ld_k = n;
+    rc = pck_solve_cascade(net, cond, prm, &c2, &so, stream);
+    if (rc) return rc;
+    return launch_cascade_drc_at(net, cond, kf, kr, n, c2.y_cells, c2.ld_yc, c2.cells, c2.status_cells, c2.ld_c, obj, out,
+                                 order_in, ld_oi, s);
 }
 
 // ----------------------------------------------------------------------------

@@ -615,6 +615,84 @@ class DeviceNetwork:
                                                _ptr(out['nsteps']), _stream(torch)))
         return out
 
+    def _cascade_drc_fn(self, name):
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise RuntimeError('pycatkin_amd: %s lacks %s (the bed DRC) -- rebuild the library '
+                               '(__graft_entry__.build())' % (L.LIB_PATH, name))
+        return fn
+
+    def cascade_drc_at(self, n, T, p, y_cells, kf, kr, wr=None, wy=None, desc=None, fixc=None, inflow=None,
+                       status_cells=None, cells=None, want_order_in=True):
+        """pck_cascade_drc_at: the degree of rate control of K bed objectives
+        J_m = mean over the cells of wr[m] . net + wy[m] . y_outlet at the cell
+        states y_cells [cells, NDYN, n] of a reactor cascade (solve_cascade's
+        profile), kf / kr [NRXN, n]: one backward adjoint sweep through the
+        cells in one launch.  status_cells [cells, n] (optional) gates a bed
+        whose cells are not all status 0.  Returns dict(val [K, n], xi
+        [K, NRXN, n], status [n], ostatus [K, n]) and, with want_order_in,
+        order_in [K, NDYN, n] = d ln J_m / d ln inflow_i.  (cells defaults to
+        y_cells' first dimension; the library refuses a count out of range.)"""
+        torch = self.torch
+        fn = self._cascade_drc_fn('pck_cascade_drc_at')
+        ob, o, out, keep2 = self._multi_io(n, wr, wy)
+        c, keep = self.conditions(n, T, p, desc, fixc, None, inflow)
+        y = torch.as_tensor(y_cells, dtype=torch.float64, device='cuda')
+        if y.dim() != 3 or y.shape[1] != self.NDYN or y.shape[2] != n:
+            raise ValueError('y_cells has shape %s, expected (cells, %d, %d)' % (tuple(y.shape), self.NDYN, n))
+        y = y.contiguous()
+        cells = int(y.shape[0]) if cells is None else int(cells)
+        if 1 <= cells <= L.MAX_CELLS and cells > y.shape[0]:
+            raise ValueError('cells = %d, but y_cells holds %d cells' % (cells, y.shape[0]))
+        kf = torch.as_tensor(kf, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        kr = torch.as_tensor(kr, dtype=torch.float64, device='cuda').reshape(self.NRXN, n).contiguous()
+        sc = None
+        if status_cells is not None:
+            sc = torch.as_tensor(status_cells, dtype=torch.int32, device='cuda').contiguous()
+            if sc.dim() != 2 or sc.shape[0] != y.shape[0] or sc.shape[1] != n:
+                raise ValueError('status_cells has shape %s, expected (%d, %d)' % (tuple(sc.shape), y.shape[0], n))
+        oi = None
+        if want_order_in:
+            oi = torch.empty((ob.K * self.NDYN, n), dtype=torch.float64, device='cuda')
+            out['order_in'] = oi.reshape(ob.K, self.NDYN, n)
+        L.check(fn(self.h, C.byref(c), _ptr(kf), _ptr(kr), n, _ptr(y), n, cells, _ptr(sc), n, C.byref(ob), C.byref(o),
+                   _ptr(oi), n, _stream(torch)))
+        return out
+
+    def cascade_drc(self, n, T, p, y0, cells, wr=None, wy=None, desc=None, fixc=None, inflow=None, start='system',
+                    want_order_in=True, **kw):
+        """pck_cascade_drc: solve_cascade (fused; kw as for solve, newton=True
+        is required) and cascade_drc_at at its cell states, with the solve's
+        own rate constants.  Returns what cascade_drc_at returns plus nsteps
+        [n], cell_fail [n], y_cells [cells, NDYN, n] and status_cells
+        [cells, n]."""
+        torch = self.torch
+        fn = self._cascade_drc_fn('pck_cascade_drc')
+        if isinstance(start, str) and start not in L.CASCADE_START_MODES:
+            raise ValueError("start must be 'system' or 'upstream', not %r" % (start,))
+        start = L.CASCADE_START_MODES[start] if isinstance(start, str) else int(start)
+        cells = int(cells)
+        ob, o, out, keep2 = self._multi_io(n, wr, wy)
+        c, keep = self.conditions(n, T, p, desc, fixc, y0, inflow)
+        prm = self.params(**kw)
+        nc = min(max(cells, 1), L.MAX_CELLS)       # sized for the refusals too
+        out['nsteps'] = torch.empty(n, dtype=torch.int32, device='cuda')
+        out['cell_fail'] = torch.empty(n, dtype=torch.int32, device='cuda')
+        out['y_cells'] = torch.empty((nc, self.NDYN, n), dtype=torch.float64, device='cuda')
+        out['status_cells'] = torch.empty((nc, n), dtype=torch.int32, device='cuda')
+        cas = L.Cascade()
+        cas.cells, cas.start = cells, start
+        cas.cell_fail = _ptr(out['cell_fail'])
+        cas.y_cells, cas.ld_yc = _ptr(out['y_cells']), n
+        cas.status_cells, cas.ld_c = _ptr(out['status_cells']), n
+        oi = None
+        if want_order_in:
+            oi = torch.empty((ob.K * self.NDYN, n), dtype=torch.float64, device='cuda')
+            out['order_in'] = oi.reshape(ob.K, self.NDYN, n)
+        L.check(fn(self.h, C.byref(c), C.byref(prm), C.byref(cas), C.byref(ob), C.byref(o), _ptr(oi), n,
+                   _ptr(out['nsteps']), _stream(torch)))
+        return out
+
     def stability_at(self, n, T, p, y, kf, kr, desc=None, fixc=None, inflow=None, status_in=None, reduce=True,
                      re_tol=0.0, lanes=L.SENS_LANES_AUTO, want=EIG_OUTPUTS):
         """pck_stability_at: the eigenvalues of the Jacobian at the states y
